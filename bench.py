@@ -71,7 +71,13 @@ def parse():
     ap.add_argument("--cpu-probe", type=int, default=0, help=argparse.SUPPRESS)      # child of cpu_baseline (all-cores figure)
     ap.add_argument("--raw", action="store_true", help="start every step from a uint16 RGGB Bayer plane in HBM (adaisp_demosaic, "
                     "an extension: the reference's pipeline starts from RGB) instead of the fp32 RGB batch")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path "
+                    "computed in its last step as DIR/<name>.npy (float32; a fixed, seeded sample of every array, indices beside "
+                    "it as <name>_index.npy, float64; at most 64 MB in all): for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def build_workload(a, dev):
@@ -153,6 +159,7 @@ def build_workload(a, dev):
 
     def step():
         x = isp_chain()
+        step.isp_out = x                                   # under capture: the graph's own output tensor, rewritten by every replay
         with torch.no_grad():
             return engine(x)
 
@@ -1036,6 +1043,30 @@ def run_extras(dev, line):
         torch.cuda.empty_cache()
 
 
+DUMP_SAMPLES = 1 << 21      # elements kept per array: 2 arrays x 2^21 x (4 B value + 8 B index) = 48 MB in all
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> device tensor) as DIR/<name>.npy, float32. One of more than DUMP_SAMPLES
+    elements is written as a sample: the same DUMP_SAMPLES flat indices (seeded, sorted) for the same shape in every run, saved
+    beside it as DIR/<name>_index.npy (float64, exact) so that np.unravel_index(index, shape) places every value."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLES:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLES, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(os.path.join(outdir, f"{name}_index.npy"), idx.astype(np.float64))
+            total += idx.size * 8
+        v = flat.float().cpu().numpy()
+        np.save(os.path.join(outdir, f"{name}.npy"), v)
+        total += v.nbytes
+        mark(f"dumped {name}: shape {tuple(t.shape)}, {v.size} value(s)")
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def prepare_gpu_run(a, dev):
     """Workload, eager warm-up, hipGraph capture and the two-stream pipeline -> (run, single_run, graphed, pipelined, engine, x0, sched, step)."""
     step, engine, agent, x0, sched = build_workload(a, dev)
@@ -1100,6 +1131,8 @@ def main():
     dry = rehearsal == "dry"
     rehearsal = rehearsal in ("1", "dry")
     if dry:
+        if a.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs needs the device (a dry rehearsal computes nothing)")
         dev = torch.device("cpu")
     else:
         if not torch.cuda.is_available():
@@ -1145,6 +1178,11 @@ def main():
     mark(f"timed region done: {dt / a.steps * 1e3:.3f} ms per step")
     if engine is not None:
         engine.check_chains(sync=True)           # a chain wait that gave up = a wrong forward inside the timed region: raise
+    if a.dump_outputs and rank == 0:
+        # before the detail passes below reuse these buffers: the detections of the last timed step (engine.pred, what step()
+        # returns) and the ISP image that step wrote (pipelined: the hand-over buffer of the next batch, the same input)
+        isp_out = run.xbuf[(run.state["i"] - 1) & 1] if pipelined else step.isp_out
+        dump_outputs(a.dump_outputs, {"detections": engine.pred, "isp_output": isp_out})
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -1,8 +1,13 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# Before anything calls MKL: its vector math (torch-CPU exp / tanh / ...) rounds differently per CPU vendor and ISA, and
+# the bit-exact host tests compare against fixtures written in its COMPATIBLE branch, the same on every x86 host
+# (tests/golden/gen_golden.py)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):

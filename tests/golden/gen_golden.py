@@ -13,8 +13,12 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
+# MKL's vector math (torch-CPU exp / tanh / ...) rounds differently per CPU vendor and ISA; its COMPATIBLE branch is the same
+# on every x86 host, so the fixtures do not depend on the machine that wrote them (tests/conftest.py pins the same branch)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 sys.dont_write_bytecode = True
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -283,6 +287,34 @@ def gen_core():
     out["one_hot"] = agent_mod.one_hot(10, idx.to(torch.int64)).numpy()
     np.savez_compressed(os.path.join(OUT, "select.npz"), **out)
 
+
+def gen_regressor():
+    """Every filter's filter_param_regressor on the features of filters.npz (same seed, same draws), for the bit-exact host
+    test: written in MKL's COMPATIBLE branch (the top of this file), the branch tests/conftest.py pins, so the parameters are
+    the same on every x86 host. The other fixtures were written earlier in one Intel host's own branch and are kept as they
+    are: tests/parity_tolerances.json holds the GPU errors measured against them, and a rewrite moves them by roundings
+    (filters.npz's W.param is the one bit-exact array that differs between the branches)."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE"
+    filters, cfg, _, _ = import_reference()
+    classes = [
+        ("E", filters.ExposureFilter), ("G", filters.GammaFilter), ("CCM", filters.CCMFilter),
+        ("Shr", filters.SharpenFilter), ("NLM", filters.DenoiseFilter), ("T", filters.ToneFilter),
+        ("Ct", filters.ContrastFilter), ("S+", filters.SaturationPlusFilter), ("BW", filters.WNBFilter),
+        ("W", filters.ImprovedWhiteBalanceFilter), ("USM", filters.SharpenUSMFilter),
+        ("ShrV2", filters.SharpenFilterV2), ("C", filters.ColorFilter),
+    ]
+    out = {}
+    rng = np.random.default_rng(5)
+    with torch.no_grad():
+        for name, cls in classes:
+            f = cls(cfg, predict=False)
+            feat = rng.normal(0.0, 1.2, (2, f.get_num_filter_parameters())).astype(np.float32)
+            if name == "USM":
+                feat[:, 0] = np.abs(feat[:, 0]) * 0.5 + 0.2
+            key = name.replace("+", "p")
+            out[f"{key}.feat"] = feat
+            out[f"{key}.param"] = f.filter_param_regressor(torch.from_numpy(feat)).reshape(2, -1).numpy()
+    np.savez_compressed(os.path.join(OUT, "regressor.npz"), **out)
 
 
 def gen_nlm_general():
@@ -653,7 +685,7 @@ def gen_td():
     print("td.npz written:", case_no, "switch settings")
 
 
-GENERATORS = dict(core=gen_core, yolo=gen_yolo, eval=gen_eval, ckpt=gen_ckpt, replay=gen_replay, mosaic=gen_mosaic,
+GENERATORS = dict(core=gen_core, regressor=gen_regressor, yolo=gen_yolo, eval=gen_eval, ckpt=gen_ckpt, replay=gen_replay, mosaic=gen_mosaic,
                   nlm_general=gen_nlm_general, value_path=gen_value_path, midsize=gen_midsize, td=gen_td)
 _OLD_FLAGS = {"--eval-only": "eval", "--ckpt-only": "ckpt", "--replay-only": "replay", "--mosaic-only": "mosaic",
               "--midsize-only": "midsize", "--value-path-only": "value_path", "--nlm-general-only": "nlm_general"}

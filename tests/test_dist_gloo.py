@@ -6,15 +6,40 @@ import torch
 import torch.multiprocessing as mp
 
 
+# The ranks of these tests are CPU ranks over gloo (and the launchers' dry rehearsals use no device): on a box with a GPU,
+# init_from_env would put rank r on cuda:r, which a one-GPU box does not have. They must not see the GPU.
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
 
 
+def _spawn_ranks(target, world, timeout):
+    """Run `target(rank, world, port, queue)` in `world` fresh processes; returns what they put, sorted. A rank still
+    running at the end (its peer failed and it waits in a collective) is killed."""
+    ctx = mp.get_context("spawn")
+    out = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=target, args=(r, world, port, out)) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        for p in procs:
+            p.join(timeout)
+            assert p.exitcode == 0
+        return sorted(out.get(timeout=5) for _ in range(world))
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+
+
 def _worker(rank, world, port, out):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **NO_GPU)
     import torch.distributed as dist
     from adaptiveisp_amd import dist as adist
     from adaptiveisp_amd.config import cfg
@@ -76,23 +101,14 @@ def _worker(rank, world, port, out):
 
 
 def test_two_rank_gradient_all_reduce():
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, out)) for r in range(2)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    got = sorted(out.get(timeout=5) for _ in range(2))
+    got = _spawn_ranks(_worker, 2, 120)
     assert got == [(0, 1223841), (1, 1223841)]
 
 
 def _mask_worker(rank, world, port, out):
     """World 4, unequal presence masks: parameter k of a 6-layer stack has a gradient on rank r iff bit r of PATTERN[k]."""
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **NO_GPU)
     os.environ.pop("ADAISP_DP_FETCH_MASK", None)
     import torch.distributed as dist
     from adaptiveisp_amd import dist as adist
@@ -145,16 +161,7 @@ def _mask_worker(rank, world, port, out):
 
 
 def test_four_ranks_unequal_presence_masks():
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_mask_worker, args=(r, 4, port, out)) for r in range(4)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(180)
-        assert p.exitcode == 0
-    got = sorted(out.get(timeout=5) for _ in range(4))
+    got = _spawn_ranks(_mask_worker, 4, 180)
     assert [g[0] for g in got] == [0, 1, 2, 3]
 
 
@@ -199,7 +206,7 @@ def _torch_isp(img, packed, op_ids):
 
 def _rl_worker(rank, world, port, out):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), **NO_GPU)
     import torch.distributed as dist
     from adaptiveisp_amd import dist as adist
     from adaptiveisp_amd.agent import Agent
@@ -269,16 +276,7 @@ def _rl_worker(rank, world, port, out):
 def test_two_ranks_train_iteration_lock_step():
     """Config 4's N>1 path: each rank runs rl.train_iteration on its own batch; after the bucketed all-reduce + global
     clip + Adam the replicas hold bit-identical parameters and saw the same gradient norm (train.py:341-351)."""
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_rl_worker, args=(r, 2, port, out)) for r in range(2)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(300)
-        assert p.exitcode == 0
-    got = sorted(out.get(timeout=5) for _ in range(2))
+    got = _spawn_ranks(_rl_worker, 2, 300)
     assert got[0][1] == got[1][1] and got[0][1] > 0
     assert got[0][2] == got[1][2] == 20                    # 10 filters x (fc_mask.weight, fc_mask.bias): no gradient, no Adam state
 
@@ -290,7 +288,7 @@ def _run_launcher(cmd, env_extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, **env_extra)
+    env = dict(os.environ, **env_extra, **NO_GPU)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, *cmd], cwd=root, env=env, capture_output=True, text=True, timeout=300)
@@ -316,7 +314,7 @@ def test_bench_rejects_a_world_that_is_not_gpus():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, BENCH_REHEARSAL="dry", WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
+    env = dict(os.environ, BENCH_REHEARSAL="dry", WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", **NO_GPU)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1"], cwd=root, env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
 

@@ -21,7 +21,7 @@ CLASSES = {"E": F.ExposureFilter, "G": F.GammaFilter, "CCM": F.CCMFilter, "Shr":
 
 @pytest.mark.parametrize("name", sorted(CLASSES))
 def test_regressor_matches_reference(golden, name):
-    g = golden("filters")
+    g = golden("regressor")                              # written in the MKL branch tests/conftest.py pins (gen_golden.py)
     f = CLASSES[name](cfg, predict=False)
     with torch.no_grad():
         p = f.filter_param_regressor(T(g[f"{name}.feat"])).reshape(2, -1).numpy()
