@@ -14,6 +14,7 @@ bias + SiLU + residual epilogue:
 
 There is no eager fallback: without libadayolo.so / a HIP device this raises.
 """
+import collections
 import ctypes
 import os
 
@@ -52,6 +53,88 @@ def _pack_conv(w, b, pad_cout_to=None):
 
 
 BNECK_WS_DEFAULT = "1"       # whole-Bottleneck launches for the C = 64 / 128 stages (YoloEngine.fuse_bottlenecks_ws)
+
+# A "conv" plan entry holds adayolo_conv_fwd_variant's argument list (include/adayolo.h) as it is launched:
+#   in, in_cstride, weight, bias, residual, res_cstride, out, out_cstride, B, H, W, Cin, Cout, ksize, stride, act, variant
+# ("conv2", fuse_pairs: the first 16, then the fused 1x1's weight, bias, out, out_cstride, Cout). The positions code names:
+ARG_RES, ARG_OUT, ARG_SHAPE, ARG_K, ARG_VARIANT = 4, 6, 8, 13, 16
+
+
+class ConvShape(collections.namedtuple("ConvShape", "B H W cin cout k s act variant Ho Wo flops inp in_cs weight res res_cs "
+                                                    "out out_cs")):
+    __slots__ = ()
+
+    @property
+    def key(self):
+        """B, H, W, Cin, Cout, k, s, act: the tuning table's key."""
+        return tuple(self[:8])
+
+
+def _conv_shape(args, kind="conv"):
+    """The named view of a "conv" / "conv2" entry's argument list: its shape, kernel variant (None for "conv2": that launch
+    takes none), output size, flops (of both layers for "conv2") and the pointer values of the tensors it reads and writes."""
+    B, H, W, cin, cout, k, s, act = args[ARG_SHAPE:ARG_VARIANT]
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    fused = args[-1] if kind == "conv2" else 0                # the fused 1x1's Cout
+    res = args[ARG_RES]
+    return ConvShape(B, H, W, cin, cout, k, s, act, None if kind == "conv2" else args[ARG_VARIANT], Ho, Wo,
+                     2.0 * B * Ho * Wo * cout * (k * k * cin + fused), args[0].value, args[1], args[2].value,
+                     res.value if res is not None else None, args[ARG_RES + 1], args[ARG_OUT].value, args[ARG_OUT + 1])
+
+
+# ---- conv kernel variants (include/adayolo.h)
+SPLITK_BASE = 100                                        # variant 100 + S = variant 60 with S ranges of k-tiles
+SPLITK_CANDIDATES = (102, 103, 104, 106, 108, 112, 116)
+TUNE_CANDIDATES = (2, 5, 22, 26, 27, 40, 50, 60, 80, 85, 90) + SPLITK_CANDIDATES
+S2GRAD_VARIANTS = (5, 22, 26, 27, 60) + SPLITK_CANDIDATES     # kernels that serve adayolo_conv_s2grad_fwd (listed with k = 2)
+KEEP_VARIANTS = (5, 22, 26, 27, 60, 80, 85) + SPLITK_CANDIDATES   # epilogue stores the pre-activation beside the activation
+
+
+def serves(variant, shape):
+    """Whether kernel `variant` can run a conv of `shape` (B, H, W, Cin, Cout, k, s, act: the tuning key) by its family's
+    host-side rule. k = 2 is the training engine's stride-2 data gradient (YoloEngine._conv_launch). A split-K variant also
+    needs the library to size a workspace for the shape (YoloEngine._splitk_bytes)."""
+    _, _, _, cin, cout, k, s, act = shape
+    if k == 2 and variant not in S2GRAD_VARIANTS:
+        return False                                     # the kernels with the depth-to-space epilogue
+    if 40 <= variant < 50:
+        return k == 3 and cin in (32, 64)                # whole-K-resident kernels: 3x3 with Cin 32 / 64
+    if 50 <= variant < 60:
+        return cin % 64 == 0 and cout % 256 == 0         # ping-pong kernel
+    if 60 <= variant < 80:
+        return cin % 64 == 0 and cout % 128 == 0         # 256x128 ping-pong kernel
+    if 80 <= variant < 90:
+        return cin % 32 == 0 and cout % 128 == 0         # 256x128, two workgroups per CU
+    if 90 <= variant < 100:                              # weights-in-registers kernel: 3x3 s1, Cin 32 / 64, SiLU
+        return k == 3 and s == 1 and cin in (32, 64) and cout % 64 == 0 and act == _lib.ACT_SILU
+    return True
+
+
+def _rewrite_pairs(plan, first, match):
+    """Offer every two adjacent "conv" entries of `plan` from index `first` on to `match(a, b, x, y)` (their argument lists and
+    _conv_shape views), which returns the one entry that replaces both, or None. Returns (new plan, pairs replaced)."""
+    out, i, n = [], 0, 0
+    while i < len(plan):
+        if i >= first and i + 1 < len(plan) and plan[i][0] == plan[i + 1][0] == "conv":
+            a, b = plan[i][2], plan[i + 1][2]
+            e = match(a, b, _conv_shape(a), _conv_shape(b))
+            if e is not None:
+                out.append(e)
+                i, n = i + 2, n + 1
+                continue
+        out.append(plan[i])
+        i += 1
+    return out, n
+
+
+def _is_bottleneck(x, y):
+    """x and y (_conv_shape views) are one Bottleneck: cv1 (1x1 C -> C/2 + SiLU) and cv2 (3x3 C/2 -> C + SiLU + the block's
+    input), y reading exactly x's output and x's input, and not writing over that input."""
+    C = x.cin
+    return ((x.cout, x.k, x.s, x.act, x.res) == (C // 2, 1, 1, _lib.ACT_SILU, None) and
+            (y.cin, y.cout, y.k, y.s, y.act) == (C // 2, C, 3, 1, _lib.ACT_SILU) and
+            (y.inp, y.in_cs, y.res, y.res_cs) == (x.out, x.out_cs, x.inp, x.in_cs) and
+            (y.B, y.H, y.W) == (x.B, x.H, x.W) and y.out != x.inp)
 
 
 class YoloEngine:
@@ -99,6 +182,13 @@ class YoloEngine:
             raise ValueError(f"head_chunks={head_chunks} does not divide the batch {self.B}")
         self.head_chunks = int(head_chunks)
 
+    @property
+    def head_entries(self):
+        """Leading plan entries the head covers: the stem, the first down-sampling conv and, when k_stem_down computes it as
+        well, the 1x1 after it. The fused head launches them as one kernel and the chunked one addresses them by index, so no
+        plan rewrite touches them."""
+        return 3 if self._head_next is not None else 2
+
     # ------------------------------------------------------------------------------------------
     def _new(self, H, W, C):
         """An NHWC bf16 buffer [B,H,W,C]. With `self._shared = (parent, first)` — an engine built over the same model with a
@@ -118,17 +208,19 @@ class YoloEngine:
         self._keep.append(t)
         return t
 
+    def _conv_args(self, src, w, b, dst, k, s, act, res, cout, variant=0):
+        return [ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(b.data_ptr()),
+                ctypes.c_void_p(res.ptr) if res is not None else None, res.cs if res is not None else 0,
+                ctypes.c_void_p(dst.ptr), dst.cs, self.B, src.H, src.W, src.C, cout, k, s, act, variant]
+
     def _conv_op(self, src, conv_w, conv_b, dst, k, s, act, res=None, cout=None):
         w, b = conv_w.to(self.dev), conv_b.to(self.dev)
         self._keep += [w, b]
         cout = cout if cout is not None else w.shape[0]
-        args = [ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                ctypes.c_void_p(res.ptr) if res is not None else None, res.cs if res is not None else 0,
-                ctypes.c_void_p(dst.ptr), dst.cs, self.B, src.H, src.W, src.C, cout, k, s, act, 0]   # last: variant
+        args = self._conv_args(src, w, b, dst, k, s, act, res, cout)
         self.plan.append(("conv", self._conv_launch, args))
         self.ops.append(dict(kind="conv", src=src, dst=dst, res=res, w=w, b=b, k=k, s=s, act=act, cout=cout))
-        flops = 2.0 * self.B * dst.H * dst.W * cout * k * k * src.C
-        self.flops += flops
+        self.flops += _conv_shape(args).flops
 
     @staticmethod
     def _fused_stem_ok(m):
@@ -243,48 +335,57 @@ class YoloEngine:
         self.views = view
 
     # ------------------------------------------------------------------------------------------
-    SPLITK_BASE = 100                                    # include/adayolo.h: variant 100 + S = variant 60 with S ranges of k-tiles
-    SPLITK_CANDIDATES = (102, 103, 104, 106, 108, 112, 116)
-    TUNE_CANDIDATES = (2, 5, 22, 26, 27, 40, 50, 60, 80, 85, 90) + SPLITK_CANDIDATES
-
     def _plans(self):
         return [self.plan]
 
     # ---- split-K launches take a workspace (fp32 partial tiles + tickets): one per engine, sized for every conv of its
     #      plans and every split the library serves for it; zeroed once, the kernels leave the tickets zero
     def _splitk_bytes(self, args, variant):
-        return int(self.L.adayolo_conv_splitk_workspace_bytes(*args[8:15], variant))
+        x = _conv_shape(args)
+        return int(self.L.adayolo_conv_splitk_workspace_bytes(x.B, x.H, x.W, x.cin, x.cout, x.k, x.s, variant))
 
     def _splitk_workspace(self):
         ws = getattr(self, "_splitk_ws", None)
         if ws is None:
-            need = 0
-            for plan in self._plans():
-                for kind, _, args in plan:
-                    if kind == "conv":
-                        need = max([need] + [self._splitk_bytes(args, v) for v in self.SPLITK_CANDIDATES])
+            need = max([self._splitk_bytes(args, v) for plan in self._plans() for kind, _, args in plan if kind == "conv"
+                        for v in SPLITK_CANDIDATES], default=0)
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.AdayoloError("split-K workspace requested inside a graph capture: run the engine once before capturing")
             t = torch.zeros(max(need, 16), dtype=torch.uint8, device=self.dev)
             ws = self._splitk_ws = (t, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(t.numel()))
         return ws
 
+    @staticmethod
+    def _best_ms(fn, args, reps):
+        """Best of `reps` single launches of fn(*args) on the current stream, after one unmeasured launch (ms)."""
+        st = _lib.stream_ptr()
+        fn(*args, st)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t = float("inf")
+        for _ in range(reps):
+            e0.record()
+            fn(*args, st)
+            e1.record()
+            e1.synchronize()
+            t = min(t, e0.elapsed_time(e1))
+        return t
+
     def _tune_penalty(self, key, variant):
         """ms added to a candidate's measured time (what choosing it costs elsewhere; the training engine's forward)."""
         return 0.0
 
-    S2GRAD_VARIANTS = (5, 22, 26, 27, 60) + SPLITK_CANDIDATES     # kernels that serve adayolo_conv_s2grad_fwd (listed with k = 2)
-
     def _conv_launch(self, *a):
         """adayolo_conv_fwd_variant's argument list (17 + stream); the split-K variants go to their own entry point, and
         k = 2 is the training engine's stride-2 data gradient (adayolo_conv_s2grad_fwd: H x W its Ho x Wo grid, Cin the
-        layer's output channels, Cout 4 x its input channels)."""
-        if a[13] == 2:
-            ptr, nbytes = (self._splitk_workspace()[1:]) if a[16] >= self.SPLITK_BASE else (None, 0)
-            return self.L.adayolo_conv_s2grad_fwd(*a[:8], None, 0, None, 0, a[8], a[9], a[10], a[11], a[12] // 4, a[16], ptr, nbytes, a[17])
-        if a[16] >= self.SPLITK_BASE:
-            _, ptr, nbytes = self._splitk_workspace()
-            return self.L.adayolo_conv_splitk_fwd(*a[:8], None, 0, *a[8:17], ptr, nbytes, a[17])
+        layer's output channels, Cout 4 x its input channels). Called for every launch of a forward: reads its arguments
+        by position, not through _conv_shape."""
+        v, st = a[ARG_VARIANT:]
+        ws = self._splitk_workspace()[1:] if v >= SPLITK_BASE else (None, 0)
+        if a[ARG_K] == 2:
+            B, H, W, cin, cout = a[ARG_SHAPE:ARG_K]
+            return self.L.adayolo_conv_s2grad_fwd(*a[:ARG_SHAPE], None, 0, None, 0, B, H, W, cin, cout // 4, v, *ws, st)
+        if v >= SPLITK_BASE:
+            return self.L.adayolo_conv_splitk_fwd(*a[:ARG_SHAPE], None, 0, *a[ARG_SHAPE:ARG_VARIANT + 1], *ws, st)
         return self.L.adayolo_conv_fwd_variant(*a)
 
     def autotune(self, reps=5, cache=None, retune=False, write=True):
@@ -294,63 +395,37 @@ class YoloEngine:
         (atomically; `write=False` for ranks other than 0 of a multi-process job); `retune` measures all of them."""
         import json
         import os
-        st = _lib.stream_ptr()
         chosen = {}
-        entries = [e for plan in self._plans() for e in plan]
-        keys = {tuple(args[8:16]) for kind, _, args in entries if kind == "conv"}
+        convs = [(fn, args) for plan in self._plans() for kind, fn, args in plan if kind == "conv"]
+        keys = {_conv_shape(args).key for _, args in convs}
         if cache and os.path.exists(cache) and not retune:
             try:
                 table = {tuple(int(x) for x in k.split(",")): int(v) for k, v in json.load(open(cache)).items()}
             except Exception:
                 table = {}
             # a table written by an older build may name variants this library no longer has: treat them as missing
-            table = {k: v for k, v in table.items() if v in self.TUNE_CANDIDATES}
+            table = {k: v for k, v in table.items() if v in TUNE_CANDIDATES}
             chosen = {k: table[k] for k in keys if k in table}       # only the layer shapes the table lacks are measured
             if len(chosen) == len(keys):
-                for kind, fn, args in entries:
-                    if kind == "conv":
-                        args[16] = chosen[tuple(args[8:16])]
+                for _, args in convs:
+                    args[ARG_VARIANT] = chosen[_conv_shape(args).key]
                 self.tuned = chosen
                 self.fuse_pairs()
                 return self.tuned
         with torch.cuda.device(self.dev):
-            for kind, fn, args in entries:
-                if kind != "conv":
-                    continue
-                key = tuple(args[8:16])                      # B,H,W,Cin,Cout,k,s,act
+            for fn, args in convs:
+                key = _conv_shape(args).key
                 if key not in chosen:
                     best = (None, float("inf"))
-                    for v in self.TUNE_CANDIDATES:
-                        if 40 <= v < 50 and not (args[13] == 3 and args[11] in (32, 64)):
-                            continue                             # whole-K-resident kernels: 3x3 with Cin 32 / 64
-                        if 50 <= v < 60 and (args[11] % 64 or args[12] % 256):
-                            continue                             # ping-pong kernel: Cin % 64 == 0, Cout % 256 == 0
-                        if 60 <= v < 80 and (args[11] % 64 or args[12] % 128):
-                            continue                             # 256x128 ping-pong kernel: Cin % 64 == 0, Cout % 128 == 0
-                        if 80 <= v < 90 and (args[11] % 32 or args[12] % 128):
-                            continue                             # 256x128, two workgroups per CU: Cin % 32 == 0, Cout % 128 == 0
-                        if 90 <= v < 100 and not (args[13] == 3 and args[14] == 1 and args[11] in (32, 64) and args[12] % 64 == 0 and
-                                                  args[15] == _lib.ACT_SILU):
-                            continue                             # weights-in-registers kernel: 3x3 s1, Cin 32 / 64
-                        if v >= self.SPLITK_BASE and self._splitk_bytes(args, v) == 0:
-                            continue                             # this split does not serve the shape
-                        if args[13] == 2 and v not in self.S2GRAD_VARIANTS:
-                            continue                             # stride-2 data gradient: the kernels with that epilogue
-                        args[16] = v
-                        fn(*args, st)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        t = float("inf")
-                        for _ in range(reps):                     # best of `reps` single launches
-                            e0.record()
-                            fn(*args, st)
-                            e1.record()
-                            e1.synchronize()
-                            t = min(t, e0.elapsed_time(e1))
-                        t += self._tune_penalty(key, v)
+                    for v in TUNE_CANDIDATES:
+                        if not serves(v, key) or (v >= SPLITK_BASE and self._splitk_bytes(args, v) == 0):
+                            continue
+                        args[ARG_VARIANT] = v
+                        t = self._best_ms(fn, args, reps) + self._tune_penalty(key, v)
                         if t < best[1]:
                             best = (v, t)
                     chosen[key] = best[0]
-                args[16] = chosen[key]
+                args[ARG_VARIANT] = chosen[key]
         self.tuned = chosen
         self.fuse_pairs()
         if cache and write:
@@ -372,6 +447,10 @@ class YoloEngine:
     # ------------------------------------------------------------------------------------------
     _pair_fusion = True                                  # (the eval plan only: the training engine's tfwd / tbwd lists are separate)
 
+    def _weight(self, x):
+        """The packed weight tensor a conv (_conv_shape view) reads."""
+        return next(o["w"] for o in self.ops if o["kind"] == "conv" and o["w"].data_ptr() == x.weight)
+
     def fuse_pairs(self):
         """Bottleneck.cv2 of one block + Bottleneck.cv1 of the next in ONE launch (adayolo_conv_fused1x1_fwd) wherever the
         first conv runs on the 256 x 256 kernel (variant 50) with all its 256 output channels in one tile and the second is
@@ -384,27 +463,18 @@ class YoloEngine:
             self.fuse_bottlenecks()
         if not self._pair_fusion or os.environ.get("ADAYOLO_FUSE_1X1", "1") != "1":
             return 0
-        out, i, n, P = [], 0, 0, self.plan
-        first_free = 3 if self._head_next is not None else 2      # the head's launches are addressed by plan index
-        while i < len(P):
-            kind, fn, a = P[i]
-            if i >= first_free and kind == "conv" and i + 1 < len(P) and P[i + 1][0] == "conv":
-                b = P[i + 1][2]
-                Ho, Wo = (a[9] - 1) // a[14] + 1, (a[10] - 1) // a[14] + 1
-                if (a[12] == 256 and a[16] == 50 and a[11] % 64 == 0 and b[11] == 256 and b[12] == 128 and b[13] == 1 and
-                        b[14] == 1 and b[15] == _lib.ACT_SILU and b[4] is None and b[0].value == a[6].value and
-                        b[1] == a[7] and (b[8], b[9], b[10]) == (a[8], Ho, Wo)):
-                    # the second layer's weights in the fragment-major order the fused epilogue loads (include/adayolo.h)
-                    w2 = next(o["w"] for o in self.ops if o["kind"] == "conv" and o["w"].data_ptr() == b[2].value)
-                    w2p = w2.reshape(4, 32, 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
-                    self._keep.append(w2p)
-                    out.append(("conv2", self.L.adayolo_conv_fused1x1_fwd,
-                                list(a[:16]) + [ctypes.c_void_p(w2p.data_ptr()), b[3], b[6], b[7], 128]))
-                    i, n = i + 2, n + 1
-                    continue
-            out.append(P[i])
-            i += 1
-        self.plan = out
+
+        def match(a, b, x, y):
+            if (x.variant == 50 and x.cout == 256 and x.cin % 64 == 0 and
+                    (y.cin, y.cout, y.k, y.s, y.act, y.res) == (256, 128, 1, 1, _lib.ACT_SILU, None) and
+                    (y.inp, y.in_cs, y.B, y.H, y.W) == (x.out, x.out_cs, x.B, x.Ho, x.Wo)):
+                # the second layer's weights in the fragment-major order the fused epilogue loads (include/adayolo.h)
+                w2p = self._weight(y).reshape(4, 32, 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
+                self._keep.append(w2p)
+                return ("conv2", self.L.adayolo_conv_fused1x1_fwd,
+                        list(a[:ARG_VARIANT]) + [ctypes.c_void_p(w2p.data_ptr()), b[3], b[6], b[7], 128])
+
+        self.plan, n = _rewrite_pairs(self.plan, self.head_entries, match)
         self.fused_pairs += n
         self.fuse_chains()
         self.fuse_k1()
@@ -421,21 +491,20 @@ class YoloEngine:
         self.k1_layers = getattr(self, "k1_layers", 0)
         if os.environ.get("ADAYOLO_K1", "0") != "1" or not self._pair_fusion:
             return 0
-        first_free = 3 if self._head_next is not None else 2
         n = 0
         for i, (kind, fn, a) in enumerate(self.plan):
-            if i < first_free or kind != "conv":
+            if i < self.head_entries or kind != "conv":
                 continue
-            if not (a[13] == 1 and a[14] == 1 and a[4] is None and a[11] in (256, 512) and a[12] % 256 == 0):
+            x = _conv_shape(a)
+            if not (x.k == 1 and x.s == 1 and x.res is None and x.cin in (256, 512) and x.cout % 256 == 0):
                 continue
-            w = next(o["w"] for o in self.ops if o["kind"] == "conv" and o["w"].data_ptr() == a[2].value)
-            cout, cin = a[12], a[11]
-            if w.shape[0] != cout or w.numel() != cout * cin:
+            w = self._weight(x)
+            if w.shape[0] != x.cout or w.numel() != x.cout * x.cin:
                 continue
-            wp = w.reshape(cout // 32, 32, cin // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()   # fragment-major (include/adayolo.h)
+            wp = w.reshape(x.cout // 32, 32, x.cin // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()   # fragment-major (include/adayolo.h)
             self._keep.append(wp)
-            self.plan[i] = ("k1", self.L.adayolo_conv1x1_stream_fwd,
-                            [a[0], a[1], ctypes.c_void_p(wp.data_ptr()), a[3], a[6], a[7], a[8], a[9], a[10], cin, cout, a[15]])
+            self.plan[i] = ("k1", self.L.adayolo_conv1x1_stream_fwd, [a[0], a[1], ctypes.c_void_p(wp.data_ptr()), a[3], a[6], a[7],
+                                                                       x.B, x.H, x.W, x.cin, x.cout, x.act])
             n += 1
         self.k1_layers += n
         return n
@@ -456,17 +525,14 @@ class YoloEngine:
         if os.environ.get("ADAYOLO_CHAIN", "1") != "1":
             return 0
         P, out, i, made = self.plan, [], 0, 0
-        first_free = 3 if self._head_next is not None else 2
+        shapes = [_conv_shape(a, kind) if kind in ("conv", "conv2") else None for kind, _, a in P]
 
         def eligible(j):
-            kind, _, a = P[j]
-            if j < first_free:
+            x = shapes[j]
+            if j < self.head_entries or x is None:
                 return False
-            if kind == "conv2":
-                return True
-            if kind != "conv" or a[11] % 64:
-                return False
-            return (a[16] == 50 and a[12] % 256 == 0) or (a[16] == 60 and a[12] % 128 == 0)
+            return P[j][0] == "conv2" or (x.cin % 64 == 0 and ((x.variant == 50 and x.cout % 256 == 0) or
+                                                               (x.variant == 60 and x.cout % 128 == 0)))
 
         # What a chain can win is the partly empty LAST round of every layer (460 tiles on 256 CUs: the next layer's tiles fill it)
         # and the launch boundaries; a layer with FEWER tiles than CUs has no second round to fill, and its successor cannot start
@@ -476,10 +542,8 @@ class YoloEngine:
         cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
 
         def tiles(j):
-            kind, _, a = P[j]
-            Ho, Wo = (a[9] - 1) // a[14] + 1, (a[10] - 1) // a[14] + 1
-            bn = 128 if (kind == "conv" and a[16] == 60) else 256
-            return ((a[8] * Ho * Wo + 255) // 256) * (a[12] // bn)
+            x = shapes[j]
+            return ((x.B * x.Ho * x.Wo + 255) // 256) * (x.cout // (128 if x.variant == 60 else 256))
 
         if os.environ.get("ADAYOLO_CHAIN_ALL", "0") == "1":      # measurement: every eligible run, whatever its tile counts
             cus = 0
@@ -492,16 +556,10 @@ class YoloEngine:
                 flops = 0.0
                 for k in range(n):
                     kind, _, a = P[i + k]
-                    ly = layers[k]
-                    ly.in_, ly.in_cstride, ly.weight, ly.bias = a[0], a[1], a[2], a[3]
-                    ly.residual, ly.res_cstride, ly.out, ly.out_cstride = a[4], a[5], a[6], a[7]
-                    ly.B, ly.H, ly.W, ly.Cin, ly.Cout, ly.ksize, ly.stride, ly.act = a[8:16]
-                    ly.tile = 1 if (kind == "conv" and a[16] == 60) else 0
-                    Ho, Wo = (a[9] - 1) // a[14] + 1, (a[10] - 1) // a[14] + 1
-                    flops += 2.0 * a[8] * Ho * Wo * a[12] * a[13] * a[13] * a[11]
-                    if kind == "conv2":
-                        ly.weight2, ly.bias2, ly.out2, ly.out2_cstride, ly.Cout2 = a[16], a[17], a[18], a[19], a[20]
-                        flops += 2.0 * a[8] * Ho * Wo * a[12] * a[20]
+                    x = shapes[i + k]
+                    # a chain layer's fields: the conv's arguments up to act, then those of a fused 1x1 ("conv2")
+                    layers[k] = _lib.ChainLayer(*(a if kind == "conv2" else a[:ARG_VARIANT]), tile=int(x.variant == 60))
+                    flops += x.flops
                 nbytes = int(self.L.adayolo_conv_chain_workspace_bytes(layers, n))
                 if nbytes:
                     ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
@@ -551,25 +609,13 @@ class YoloEngine:
         self.fused_ws_blocks = getattr(self, "fused_ws_blocks", 0)
         if os.environ.get("ADAYOLO_BNECK_WS", BNECK_WS_DEFAULT) != "1":
             return 0
-        out, i, n, P = [], 0, 0, self.plan
-        first_free = 3 if self._head_next is not None else 2
-        while i < len(P):
-            kind, fn, a = P[i]
-            if i >= first_free and kind == "conv" and i + 1 < len(P) and P[i + 1][0] == "conv":
-                b = P[i + 1][2]
-                C = a[11]
-                if (C in (64, 128) and (a[12], a[13], a[14], a[15]) == (C // 2, 1, 1, _lib.ACT_SILU) and a[4] is None and
-                        (b[11], b[12], b[13], b[14], b[15]) == (C // 2, C, 3, 1, _lib.ACT_SILU) and b[4] is not None and
-                        b[4].value == a[0].value and b[5] == a[1] and b[0].value == a[6].value and b[1] == a[7] and
-                        (b[8], b[9], b[10]) == (a[8], a[9], a[10]) and b[6].value != a[0].value and
-                        2 * a[8] * a[9] * a[10] * max(a[1], b[7]) + 256 <= 0xFFFFFF00):
-                    out.append(("bneckws", self.L.adayolo_bottleneck_ws_fwd,
-                                [a[0], a[1], a[2], a[3], b[2], b[3], b[6], b[7], a[8], a[9], a[10], C]))
-                    i, n = i + 2, n + 1
-                    continue
-            out.append(P[i])
-            i += 1
-        self.plan = out
+
+        def match(a, b, x, y):
+            if x.cin in (64, 128) and _is_bottleneck(x, y) and 2 * x.B * x.H * x.W * max(x.in_cs, y.out_cs) + 256 <= 0xFFFFFF00:
+                return ("bneckws", self.L.adayolo_bottleneck_ws_fwd,
+                        [a[0], a[1], a[2], a[3], b[2], b[3], b[6], b[7], x.B, x.H, x.W, x.cin])
+
+        self.plan, n = _rewrite_pairs(self.plan, self.head_entries, match)
         self.fused_ws_blocks += n
         return n
 
@@ -581,23 +627,12 @@ class YoloEngine:
         self.fused_blocks = getattr(self, "fused_blocks", 0)
         if os.environ.get("ADAYOLO_BNECK", "0") != "1":
             return 0
-        out, i, n, P = [], 0, 0, self.plan
-        first_free = 3 if self._head_next is not None else 2
-        while i < len(P):
-            kind, fn, a = P[i]
-            if i >= first_free and kind == "conv" and i + 1 < len(P) and P[i + 1][0] == "conv":
-                b = P[i + 1][2]
-                if ((a[11], a[12], a[13], a[14], a[15]) == (256, 128, 1, 1, _lib.ACT_SILU) and a[4] is None and
-                        (b[11], b[12], b[13], b[14], b[15]) == (128, 256, 3, 1, _lib.ACT_SILU) and b[4] is not None and
-                        b[4].value == a[0].value and b[5] == a[1] and b[0].value == a[6].value and b[1] == a[7] and a[7] == 128 and
-                        (b[8], b[9], b[10]) == (a[8], a[9], a[10]) and b[6].value != a[0].value):
-                    out.append(("bneck", self.L.adayolo_bottleneck256_fwd,
-                                [a[0], a[1], a[2], a[3], b[2], b[3], b[6], b[7], a[8], a[9], a[10]]))
-                    i, n = i + 2, n + 1
-                    continue
-            out.append(P[i])
-            i += 1
-        self.plan = out
+
+        def match(a, b, x, y):
+            if x.cin == 256 and x.out_cs == 128 and _is_bottleneck(x, y):
+                return ("bneck", self.L.adayolo_bottleneck256_fwd, [a[0], a[1], a[2], a[3], b[2], b[3], b[6], b[7], x.B, x.H, x.W])
+
+        self.plan, n = _rewrite_pairs(self.plan, self.head_entries, match)
         self.fused_blocks += n
         return n
 
@@ -632,10 +667,8 @@ class YoloEngine:
 
     def num_launches(self):
         """Launches one forward issues (the hook's index range)."""
-        if self._stem is None:
-            return len(self.plan)
-        if self.fuse_head:
-            return 1 + len(self.plan) - (3 if self._head_next is not None else 2)
+        if self._stem is not None and self.fuse_head:
+            return 1 + len(self.plan) - self.head_entries
         return len(self.plan)
 
     def forward(self, img):
@@ -677,7 +710,7 @@ class YoloEngine:
             hook = self.hook
             if hook is not None:
                 hook(0)
-            for li, (kind, fn, args) in enumerate(self.plan[(3 if n else 2):]):
+            for li, (kind, fn, args) in enumerate(self.plan[self.head_entries:]):
                 rc = fn(*args, st)
                 if rc != 0:
                     _lib.check(rc, f"adayolo {kind}")
@@ -695,12 +728,10 @@ class YoloEngine:
                 _lib.check(rc, "adayolo stem")
             if nc > 1:
                 _, fn, args = self.plan[1]
-                a = list(args)
-                H, W, s = a[9], a[10], a[14]
-                Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-                a[0] = ctypes.c_void_p(a[0].value + c * Bc * H * W * a[1] * 2)
-                a[6] = ctypes.c_void_p(a[6].value + c * Bc * Ho * Wo * a[7] * 2)
-                a[8] = Bc
+                x, a = _conv_shape(args), list(args)
+                a[0] = ctypes.c_void_p(x.inp + c * Bc * x.H * x.W * x.in_cs * 2)
+                a[ARG_OUT] = ctypes.c_void_p(x.out + c * Bc * x.Ho * x.Wo * x.out_cs * 2)
+                a[ARG_SHAPE] = Bc                                 # B
                 rc = fn(*a, st)
                 if rc != 0:
                     _lib.check(rc, "adayolo conv")

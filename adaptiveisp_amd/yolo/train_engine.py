@@ -20,7 +20,19 @@ import os
 import torch
 
 from . import _lib
-from .engine import LETTERBOX_VALUE, YoloEngine, _View
+from .engine import (ARG_OUT, ARG_RES, ARG_SHAPE, ARG_VARIANT, KEEP_VARIANTS, LETTERBOX_VALUE, SPLITK_BASE, YoloEngine, _View,
+                     _conv_shape)
+
+
+def _variant_sig(*plans):
+    """The kernel variants of the plans' conv launches (a plan built before autotune changed one is rebuilt). Called per pass:
+    reads the position, not _conv_shape."""
+    return tuple(args[ARG_VARIANT] for plan in plans for kind, _, args in plan if kind == "conv")
+
+
+# adayolo_conv_dsilu_fwd's argument list: the conv's up to out_cstride, the pre-activation and its gradient (+ strides), then
+# B, H, W, Cin, Cout, k, s (no act) and the variant from this position
+DSILU_SHAPE = ARG_SHAPE + 4
 
 
 class YoloTrainEngine(YoloEngine):
@@ -40,10 +52,7 @@ class YoloTrainEngine(YoloEngine):
         return _View(self._new(H, W, C), 0, C)
 
     def _conv_entry(self, src, w, b, dst, k, s, act, res, cout, variant=0):
-        args = [ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                ctypes.c_void_p(res.ptr) if res is not None else None, res.cs if res is not None else 0,
-                ctypes.c_void_p(dst.ptr), dst.cs, self.B, src.H, src.W, src.C, cout, k, s, act, variant]
-        return ("conv", self._conv_launch, args)
+        return ("conv", self._conv_launch, self._conv_args(src, w, b, dst, k, s, act, res, cout, variant))
 
     def _build_train(self):
         L, B = self.L, self.B
@@ -203,26 +212,15 @@ class YoloTrainEngine(YoloEngine):
         """A forward conv followed by SiLU runs as ONE launch only on the kernels that can store the pre-activation
         (KEEP_VARIANTS); any other choice adds the adayolo_silu_fwd launch of that layer, whose duration is measured here
         (best of 5, once per layer shape) and added to the candidate's time."""
-        if variant in self.KEEP_VARIANTS:
+        if variant in KEEP_VARIANTS:
             return 0.0
         cost = getattr(self, "_silu_cost", None)
         if cost is None:
             cost = self._silu_cost = {}
-            st = _lib.stream_ptr()
-            for i, e in enumerate(self.tfwd[:-1]):
-                nxt = self.tfwd[i + 1]
-                k = tuple(e[2][8:16]) if e[0] == "conv" else None
-                if k is not None and k not in cost and nxt[0] == "silu" and e[2][6].value == nxt[2][0].value:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    nxt[1](*nxt[2], st)
-                    t = float("inf")
-                    for _ in range(5):
-                        e0.record()
-                        nxt[1](*nxt[2], st)
-                        e1.record()
-                        e1.synchronize()
-                        t = min(t, e0.elapsed_time(e1))
-                    cost[k] = t
+            for e, nxt in zip(self.tfwd, self.tfwd[1:]):
+                x = _conv_shape(e[2]) if e[0] == "conv" else None
+                if x is not None and x.key not in cost and nxt[0] == "silu" and x.out == nxt[2][0].value:
+                    cost[x.key] = self._best_ms(nxt[1], nxt[2], 5)
         return cost.get(key, 0.0)
 
     # ------------------------------------------------------------------------------------------
@@ -250,21 +248,18 @@ class YoloTrainEngine(YoloEngine):
             if rc != 0:
                 _lib.check(rc, f"adayolo {kind}")
 
-    # kernels whose epilogue stores the pre-activation beside the activation
-    KEEP_VARIANTS = (5, 22, 26, 27, 60, 80, 85) + YoloEngine.SPLITK_CANDIDATES
-
     def _conv_keep_launch(self, *a):
-        """adayolo_conv_keep_fwd's argument list (19 + stream); the split-K variants go to their own entry point."""
-        if a[18] >= self.SPLITK_BASE:
-            _, ptr, nbytes = self._splitk_workspace()
-            return self.L.adayolo_conv_splitk_fwd(*a[:19], ptr, nbytes, a[19])
+        """adayolo_conv_keep_fwd's argument list (19, the variant last) + stream; the split-K variants go to their own entry
+        point."""
+        if a[-2] >= SPLITK_BASE:
+            return self.L.adayolo_conv_splitk_fwd(*a[:-1], *self._splitk_workspace()[1:], a[-1])
         return self.L.adayolo_conv_keep_fwd(*a)
 
     def _forward_plan(self):
         """tfwd with every [conv -> pre-activation, SiLU(+residual)] pair whose tuned kernel can do both in one launch
         (adayolo_conv_keep_fwd, bit-identical to the pair) replaced by that launch; rebuilt when autotune changed a variant."""
         import os
-        sig = tuple(args[16] for kind, _, args in self.tfwd if kind == "conv")
+        sig = _variant_sig(self.tfwd)
         cached = getattr(self, "_tfwd_fused", None)
         if cached is not None and cached[0] == sig:
             return cached[1]
@@ -278,13 +273,12 @@ class YoloTrainEngine(YoloEngine):
                 plan.append(("stemkeep", None, nxt[2]))
                 i += 2
                 continue
-            if (fuse and e[0] == "conv" and nxt is not None and nxt[0] == "silu" and e[2][16] in self.KEEP_VARIANTS
-                    and e[2][6].value == nxt[2][0].value):        # the conv's output IS the SiLU kernel's pre-activation
+            x = _conv_shape(e[2]) if fuse and e[0] == "conv" and nxt is not None and nxt[0] == "silu" else None
+            if x is not None and x.variant in KEEP_VARIANTS and x.out == nxt[2][0].value:
+                # the conv's output IS the SiLU kernel's pre-activation (silu args: pre, pre_cs, res, res_cs, out, out_cs, npix, C):
+                # the conv's input and weights, the SiLU's residual and output, the conv's output kept as the pre-activation
                 a, sl = e[2], nxt[2]
-                # conv args: in, in_cs, w, b, res(None), 0, out(=P), out_cs, B, H, W, Cin, Cout, k, s, act(NONE), variant
-                # silu args: pre, pre_cs, res, res_cs, out, out_cs, npix, C
-                args = (a[0], a[1], a[2], a[3], sl[2], sl[3], sl[4], sl[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13],
-                        a[14], _lib.ACT_SILU, a[16])
+                args = (*a[:ARG_RES], *sl[2:6], *a[ARG_OUT:ARG_SHAPE], *x.key[:7], _lib.ACT_SILU, x.variant)
                 rc = self._conv_keep_launch(*args, _lib.stream_ptr())   # probe once: ESHAPE = this kernel does not serve the shape
                 if rc == 0:
                     plan.append(("convkeep", self._conv_keep_launch, args))
@@ -297,15 +291,13 @@ class YoloTrainEngine(YoloEngine):
         return plan
 
     def _conv_dsilu_launch(self, *a):
-        """adayolo_conv_dsilu_fwd's argument list up to `variant` (20) + stream; the workspace is the engine's. k = 2: the
-        stride-2 data gradient with the same epilogue (adayolo_conv_s2grad_fwd)."""
-        if a[17] == 2:
-            ptr, nbytes = (self._splitk_workspace()[1:]) if a[19] >= self.SPLITK_BASE else (None, 0)
-            return self.L.adayolo_conv_s2grad_fwd(*a[:12], a[12], a[13], a[14], a[15], a[16] // 4, a[19], ptr, nbytes, a[20])
-        if a[19] >= self.SPLITK_BASE:
-            _, ptr, nbytes = self._splitk_workspace()
-            return self.L.adayolo_conv_dsilu_fwd(*a[:20], ptr, nbytes, a[20])
-        return self.L.adayolo_conv_dsilu_fwd(*a[:20], None, 0, a[20])
+        """adayolo_conv_dsilu_fwd's argument list up to `variant` (20, see DSILU_SHAPE) + stream; the workspace is the
+        engine's. k = 2: the stride-2 data gradient with the same epilogue (adayolo_conv_s2grad_fwd)."""
+        B, H, W, cin, cout, k, s, v, st = a[DSILU_SHAPE:]
+        ws = self._splitk_workspace()[1:] if v >= SPLITK_BASE else (None, 0)
+        if k == 2:
+            return self.L.adayolo_conv_s2grad_fwd(*a[:DSILU_SHAPE], B, H, W, cin, cout // 4, v, *ws, st)
+        return self.L.adayolo_conv_dsilu_fwd(*a[:-1], *ws, st)
 
     def _backward_plan(self):
         """tbwd with every SiLU' launch moved into the data-gradient conv that COMPLETES the gradient it reads
@@ -317,7 +309,7 @@ class YoloTrainEngine(YoloEngine):
             its residual — the copy is gone. Only when the copy was the first write of that view and that conv the next.
         Rebuilt when autotune changed a variant; ADAYOLO_TRAIN_FUSE_DSILU=0 keeps every launch."""
         import os
-        sig = tuple(args[16] for kind, _, args in self.tbwd if kind == "conv")
+        sig = _variant_sig(self.tbwd)
         cached = getattr(self, "_tbwd_fused", None)
         if cached is not None and cached[0] == sig:
             return cached[1]
@@ -328,12 +320,17 @@ class YoloTrainEngine(YoloEngine):
         touches = lambda m, v, what: any(overlap(x, v) for x in m[what])               # noqa: E731
         drop, ds, res_from = set(), {}, {}
 
-        def fused_args(j, m, store):
+        def args_of(j):                                   # E[j]'s argument list, its residual moved to res_from[j]
             a = list(E[j][2])
             if j in res_from:
-                a[4], a[5] = ctypes.c_void_p(res_from[j].ptr), res_from[j].cs
-            return a[:6] + [a[6] if store else None, a[7] if store else 0, ctypes.c_void_p(m["P"].ptr), m["P"].cs,
-                            ctypes.c_void_p(m["dP"].ptr), m["dP"].cs] + a[8:15] + [a[16]]
+                a[ARG_RES:ARG_RES + 2] = ctypes.c_void_p(res_from[j].ptr), res_from[j].cs
+            return a
+
+        def fused_args(j, m, store):
+            a = args_of(j)
+            x = _conv_shape(a)
+            return a[:ARG_OUT] + [a[ARG_OUT] if store else None, x.out_cs if store else 0, ctypes.c_void_p(m["P"].ptr),
+                                  m["P"].cs, ctypes.c_void_p(m["dP"].ptr), m["dP"].cs] + list(x.key[:7]) + [x.variant]
 
         def served(j, m, store):                          # one real launch: the named kernel must take the shape in this form
             return self._conv_dsilu_launch(*fused_args(j, m, store), _lib.stream_ptr()) == 0
@@ -345,7 +342,8 @@ class YoloTrainEngine(YoloEngine):
                     continue
                 gy = m["gy"]
                 j = next((t for t in range(i - 1, -1, -1) if touches(M[t], gy, "writes")), None)
-                if j is None or E[j][0] != "conv" or key(M[j]["out"]) != key(gy) or E[j][2][16] not in self.KEEP_VARIANTS:
+                if (j is None or E[j][0] != "conv" or key(M[j]["out"]) != key(gy) or
+                        _conv_shape(E[j][2]).variant not in KEEP_VARIANTS):
                     continue
                 if any(touches(M[t], gy, "reads") for t in range(j + 1, i)):
                     continue
@@ -374,9 +372,7 @@ class YoloTrainEngine(YoloEngine):
             if i in ds:
                 plan.append(("convds", self._conv_dsilu_launch, fused_args(i, *ds[i])))
             elif i in res_from:
-                a = list(a)
-                a[4], a[5] = ctypes.c_void_p(res_from[i].ptr), res_from[i].cs
-                plan.append((kind, fn, a))
+                plan.append((kind, fn, args_of(i)))
             else:
                 plan.append((kind, fn, a))
         self._tbwd_fused = (sig, plan)
@@ -392,7 +388,7 @@ class YoloTrainEngine(YoloEngine):
         import os
         if os.environ.get("ADAYOLO_TRAIN_GRAPH", "1") != "1" or torch.cuda.is_current_stream_capturing():
             return None
-        sig = tuple(args[16] for kind, _, args in self.tfwd + self.tbwd if kind == "conv")    # re-capture after autotune
+        sig = _variant_sig(self.tfwd, self.tbwd)                                              # re-capture after autotune
         st = getattr(self, "_graphs", None)
         if st is None or st["sig"] != sig:
             st = self._graphs = dict(sig=sig, fwd=None, bwd=None,
@@ -644,12 +640,12 @@ class YoloTrainPairEngine:
         """Index into eng._forward_plan() of the launch that runs the (ndown + 1)-th stride-2 conv."""
         plan, seen = eng._forward_plan(), 0
         for j, (kind, _, a) in enumerate(plan):
-            if kind in ("conv", "convkeep"):
-                stride = a[14] if kind == "conv" else a[16]
-                if stride == 2:
-                    if seen == ndown:
-                        return j
-                    seen += 1
+            if kind == "convkeep":                        # a conv's arguments with the pre-activation (+ stride) before B
+                a = a[:ARG_SHAPE] + a[ARG_SHAPE + 2:]
+            if kind in ("conv", "convkeep") and _conv_shape(a).s == 2:
+                if seen == ndown:
+                    return j
+                seen += 1
         raise _lib.AdayoloError(f"YoloTrainPairEngine: the detector has fewer than {ndown + 1} stride-2 convs")
 
     def _plans_split(self):

@@ -259,3 +259,24 @@ def test_chain_run_selection():
     assert chain_runs(plan, 0, 4) == [(6, 33), (40, 44)]            # ADAYOLO_CHAIN_ALL: every eligible run of four or more
     assert chain_runs([E(460)] * 3, 256, 4) == [] and chain_runs([], 256, 4) == []
     assert chain_runs([E(100), E(460), E(460), E(460), E(460), E(100), E(100)], 256, 4) == [(1, 6)]
+
+
+def test_variant_eligibility_rule():
+    """YoloEngine.autotune's host-side rule per kernel family (yolo/engine.py::serves): every choice of the shipped tuning table
+    is served by it (split-K variants also need the library's say, so they are left out), and each family rejects a shape
+    outside its rule."""
+    from adaptiveisp_amd.yolo import engine
+    path = os.path.join(os.path.dirname(engine.__file__), "tuning", "mi355x.json")
+    table = {tuple(int(x) for x in k.split(",")): v for k, v in json.load(open(path)).items()}
+    bad = {k: v for k, v in table.items() if v < engine.SPLITK_BASE and not engine.serves(v, k)}
+    assert len(table) > 100 and not bad, bad
+    SILU, NONE = 1, 0
+    assert engine.serves(40, (8, 368, 640, 64, 32, 3, 1, NONE)) and not engine.serves(40, (8, 184, 320, 128, 64, 3, 1, NONE))
+    assert engine.serves(50, (8, 92, 160, 128, 256, 3, 1, SILU)) and not engine.serves(50, (8, 92, 160, 128, 128, 3, 1, SILU))
+    assert engine.serves(60, (8, 92, 160, 64, 128, 1, 1, SILU)) and not engine.serves(60, (8, 92, 160, 32, 128, 1, 1, SILU))
+    assert not engine.serves(80, (8, 92, 160, 48, 128, 1, 1, SILU)) and not engine.serves(85, (8, 92, 160, 64, 64, 1, 1, SILU))
+    assert engine.serves(90, (8, 368, 640, 32, 64, 3, 1, SILU)) and not engine.serves(90, (8, 368, 640, 32, 64, 3, 1, NONE))
+    assert not engine.serves(90, (8, 368, 640, 32, 64, 3, 2, SILU))
+    s2grad = (8, 128, 128, 128, 256, 2, 1, NONE)                 # stride-2 data gradient: only the kernels with that epilogue
+    assert engine.serves(27, s2grad) and engine.serves(60, s2grad) and engine.serves(102, s2grad)
+    assert not any(engine.serves(v, s2grad) for v in (2, 40, 50, 80, 85, 90))
