@@ -8,6 +8,7 @@ raise if the tensors are not on a HIP device or the library is missing.
 """
 from . import _lib  # noqa: F401
 from .config import cfg  # noqa: F401
+from .isp import image_grad  # noqa: F401
 
-__all__ = ["cfg", "_lib"]
+__all__ = ["cfg", "_lib", "image_grad"]
 __version__ = "0.1.0"

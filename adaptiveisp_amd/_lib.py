@@ -20,9 +20,9 @@ NLM_EXACT = 2      # NLM patch sums in the reference's running-sum order (slower
 NLM_SEP_V1 = 4     # the compiler-scheduled form of the separable kernel (cross-check / measurement)
 NO_USM = 8         # adaisp_forward: no image selects the unsharp mask (its empty launch is skipped)
 NLM_TILE32 = 16    # the 32-row tile of the default NLM kernel (cross-check / measurement)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -51,6 +51,10 @@ def load():
     L.adaisp_forward_uniform.restype = ci
     L.adaisp_process.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, cu, vp]
     L.adaisp_backward_params.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, cu, vp]
+    L.adaisp_backward_image.argtypes = [vp, vp, vp, vp, ci, vp, vp, ctypes.c_size_t, ci, ci, ci, cu, vp]
+    L.adaisp_backward_image.restype = ci
+    L.adaisp_backward_image_workspace_bytes.argtypes = [ci, ci, ci]
+    L.adaisp_backward_image_workspace_bytes.restype = ctypes.c_size_t
     L.adaisp_pool64.argtypes = [vp, vp, ci, ci, ci, vp]
     L.adaisp_pool64_backward.argtypes = [vp, vp, ci, ci, ci, vp]
     L.adaisp_pool64_backward.restype = ci
@@ -76,7 +80,7 @@ def load():
     L.adaisp_num_params.argtypes = [ci]
     L.adaisp_strerror.argtypes = [ci]
     L.adaisp_strerror.restype = ctypes.c_char_p
-    for name in ("adaisp_forward", "adaisp_process", "adaisp_backward_params", "adaisp_pool64", "adaisp_num_params",
+    for name in ("adaisp_forward", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_num_params",
                  "adaisp_abi_version"):
         getattr(L, name).restype = ci
     if L.adaisp_abi_version() != ABI_VERSION:
@@ -213,6 +217,29 @@ def backward_params(img, grad_out, op_ids, params, clip=True):
                                       params.data_ptr(), params.shape[1], grad.data_ptr(), B, H, W,
                                       CLIP01 if clip else 0, _stream())
     _check(rc, "adaisp_backward_params")
+    return grad
+
+
+def backward_image(img, grad_out, op_ids, params, clip=True):
+    """adaisp_backward_image: d/d img of sum(grad_out * adaisp_forward(img, op_ids, params, clip)) -> [B,3,H,W].
+    op_ids int32 [B] on the device; the workspace comes from the torch allocator (capturable in a CUDA graph)."""
+    L = load()
+    img = _dev_f32(img, "img")
+    grad_out = _dev_f32(grad_out, "grad_out")
+    B, H, W = _img_shape(img)
+    if tuple(grad_out.shape) != tuple(img.shape):
+        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    if op_ids.dtype != torch.int32 or not op_ids.is_cuda or op_ids.numel() != B:
+        raise TypeError(f"op_ids must be an int32 device tensor of {B} ids")
+    params = _dev_f32(params.reshape(B, -1), "params")
+    grad = torch.empty_like(img)
+    nbytes = int(L.adaisp_backward_image_workspace_bytes(B, H, W))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        rc = L.adaisp_backward_image(img.data_ptr(), grad_out.data_ptr(), op_ids.contiguous().data_ptr(), params.data_ptr(),
+                                     params.shape[1], grad.data_ptr(), ws.data_ptr(), nbytes, B, H, W,
+                                     CLIP01 if clip else 0, _stream())
+    _check(rc, "adaisp_backward_image")
     return grad
 
 

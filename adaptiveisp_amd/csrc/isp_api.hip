@@ -176,6 +176,26 @@ int adaisp_backward_params(const float* img, const float* grad_out, const int32_
                : ADAISP_ELAUNCH;
 }
 
+size_t adaisp_backward_image_workspace_bytes(int B, int H, int W) {
+    return (B > 0 && H > 0 && W > 0) ? backward_image_workspace_floats(B, H, W) * sizeof(float) : 0;
+}
+
+int adaisp_backward_image(const float* img, const float* grad_out, const int32_t* filter_id, const float* params,
+                          int param_stride, float* grad_img, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                          unsigned flags, void* stream) {
+    if (!img || !grad_out || !filter_id || !params || !grad_img || !workspace) return ADAISP_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || param_stride <= 0) return ADAISP_EINVAL;
+    if (B > 65535) return ADAISP_ESHAPE;
+    if (H < 3 || W < 3) return ADAISP_ESHAPE;        // as adaisp_forward: an image whose op is a stencil could not be served
+    if (workspace_bytes < adaisp_backward_image_workspace_bytes(B, H, W)) return ADAISP_EINVAL;
+    const long n = (long)B * 3 * H * W;
+    if (ranges_overlap(img, grad_img, n) || ranges_overlap(grad_out, grad_img, n)) return ADAISP_EALIAS;
+    return launch_backward_image(img, grad_out, filter_id, params, param_stride, grad_img, static_cast<float*>(workspace),
+                                 B, H, W, flags & ADAISP_CLIP01, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? ADAISP_OK
+               : ADAISP_ELAUNCH;
+}
+
 int adaisp_policy_conv(const float* in, const float* states, int n_state, const float* w, const float* bias, float* out,
                        int G, int B, int Cin, int Hin, int Cout, void* stream) {
     if (!in || !w || !bias || !out || G <= 0 || B <= 0 || Cin <= 0 || Hin <= 1 || Cout <= 0) return ADAISP_EINVAL;

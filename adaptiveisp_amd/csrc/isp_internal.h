@@ -85,6 +85,12 @@ hipError_t launch_backward_params(const float* img, const float* grad_out, const
                                   const float* params, int pstride, float* grad_params,
                                   int B, int H, int W, unsigned flags, hipStream_t s);
 
+// image gradient (isp_backward_image.hip); `workspace` holds backward_image_workspace_floats(B, H, W) floats
+size_t backward_image_workspace_floats(int B, int H, int W);
+hipError_t launch_backward_image(const float* img, const float* grad_out, const int32_t* ids, const float* params,
+                                 int pstride, float* grad_img, float* workspace, int B, int H, int W, unsigned flags,
+                                 hipStream_t s);
+
 hipError_t launch_policy_conv(const float* in, const float* states, int n_state, const float* w, const float* bias,
                               float* out, int G, int B, int Cin, int Hin, int Cout, hipStream_t s);
 hipError_t launch_policy_fc1(const float* feats, const int32_t* head_src, const float* w1, const float* b1,

@@ -30,7 +30,8 @@ class NonLocalMeansGray(nn.Module):
 
     def forward(self, rgb, h):
         if (self.search_window_size, self.patch_size) == (11, 5):
-            # the ISP's configuration: tuned kernel, differentiable in h (rgb in [0,1], as DenoiseFilter.process hands it over)
+            # the ISP's configuration: tuned kernel, differentiable in h, and in rgb inside image_grad() (rgb in [0,1], as
+            # DenoiseFilter.process hands it over)
             return isp_apply(rgb, h.reshape(h.shape[0], -1), _lib.OP_NLM, clip=False)
         if torch.is_grad_enabled() and (h.requires_grad or rgb.requires_grad):
             raise NotImplementedError("only the 11 / 5 configuration (the one on the training path) has a backward kernel")

@@ -7,7 +7,8 @@ where the pixels are touched: `process` is ONE HIP kernel launch from csrc/libad
 (op code = `Filter.op_code`, include/adaisp.h) instead of a chain of ATen ops, and `forward` fuses
 the final clip into the same launch. The small [B,n] parameter regressions (tanh_range, sigmoid,
 exp) stay in PyTorch so autograd links parameter gradients back to the heads; image gradients are
-not produced (the reference's training never needs them: train.py:341-342, imgs is a constant).
+opt-in through `adaptiveisp_amd.image_grad()` (the reference's training never needs them: train.py:341-342,
+imgs is a constant).
 """
 import math
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ADAISP_ABI_VERSION 8
+#define ADAISP_ABI_VERSION 9
 
 /* Kernel op codes. 0..9 follow the reference's default filter order (config.py:19-22). */
 enum adaisp_op {
@@ -109,6 +109,26 @@ int adaisp_backward_params(const float* img, const float* grad_out,
                            const int32_t* filter_id, const float* params, int param_stride,
                            float* grad_params,
                            int B, int H, int W, unsigned flags, void* stream);
+
+/*
+ * Image gradient of adaisp_forward: grad_img[b] = d/d img[b] of sum_px grad_out * out through the selected filter and
+ * (if ADAISP_CLIP01) the clip — what the reference's autograd gives for the filter modules (isp/filters.py, isp/sharpen.py,
+ * isp/denoise.py), subgradient conventions included: clamp / clip pass on the closed interval (the output clip :125, Gamma's
+ * clip :245, the input clips of SaturationPlus and Denoise :547,584, the tone / colour segments :300,343 — a pixel on a
+ * breakpoint takes the slope of both segments); max / min over the channels route to the first channel on ties and the hue
+ * keeps the last masked write (:455-466); the 1-px frame of the 3x3 sharpen pair passes through (isp/sharpen.py:133-138);
+ * USM's reflect padding folds back (:63-81); NLM wraps circularly and its relu passes nothing at a zero patch distance
+ * (isp/denoise.py:103-119). Parameter gradients stay with adaisp_backward_params.
+ * Every element of grad_img ([B,3,H,W]) is written; images whose op is -1 or outside enum adaisp_op get zeros. grad_img must
+ * not overlap img or grad_out (ADAISP_EALIAS). Only ADAISP_CLIP01 of `flags` has a meaning. `workspace` (at least
+ * adaisp_backward_image_workspace_bytes(B, H, W)) is caller-owned scratch; nothing is allocated or synchronised, so the
+ * call can be captured in a hipGraph. H, W >= 3 (as adaisp_forward).
+ */
+size_t adaisp_backward_image_workspace_bytes(int B, int H, int W);
+int adaisp_backward_image(const float* img, const float* grad_out,
+                          const int32_t* filter_id, const float* params, int param_stride,
+                          float* grad_img, void* workspace, size_t workspace_bytes,
+                          int B, int H, int W, unsigned flags, void* stream);
 
 /*
  * Bayer demosaic front-end — an EXTENSION (north_star's raw-Bayer entry; the reference has no demosaic, only the

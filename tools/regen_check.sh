@@ -2,12 +2,15 @@
 # Regenerates every golden fixture from /root/reference into a scratch directory and fails on ANY array difference against
 # the committed files under tests/golden/ (build container only: the reference does not travel to the GPU box).
 #   tools/regen_check.sh            # all generators
-#   tools/regen_check.sh td,yolo    # some of them
+#   tools/regen_check.sh td,yolo    # some of them (`imggrad`: tests/golden/gen_imggrad.py)
 set -e
 cd "$(dirname "$0")/.."
 OUT=$(mktemp -d /tmp/adaisp_regen.XXXXXX)
 cp tests/golden/state_dict_keys.json "$OUT"/ 2>/dev/null || true
-if [ -n "$1" ]; then python tests/golden/gen_golden.py --only "$1" --out "$OUT"; else python tests/golden/gen_golden.py --out "$OUT"; fi
+NAMES=$(echo ",${1:-}," | sed 's/,imggrad,/,/; s/^,*//; s/,*$//')
+if [ -z "${1:-}" ] || [ "$NAMES" != "${1:-}" ]; then python tests/golden/gen_imggrad.py --out "$OUT"; fi
+if [ -n "$NAMES" ]; then python tests/golden/gen_golden.py --only "$NAMES" --out "$OUT"
+elif [ -z "${1:-}" ]; then python tests/golden/gen_golden.py --out "$OUT"; fi
 python - "$OUT" <<'PY'
 import json, os, sys
 import numpy as np
