@@ -6,6 +6,7 @@ kernel from the shared library. Nothing in this module falls back to eager PyTor
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -21,8 +22,10 @@ NLM_SEP_V1 = 4     # the compiler-scheduled form of the separable kernel (cross-
 NO_USM = 8         # adaisp_forward: no image selects the unsharp mask (its empty launch is skipped)
 NLM_TILE32 = 16    # the 32-row tile of the default NLM kernel (cross-check / measurement)
 ABI_VERSION = 9
+UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
+UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -60,6 +63,8 @@ def load():
     L.adaisp_pool64_backward.restype = ci
     L.adaisp_demosaic.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
     L.adaisp_demosaic.restype = ci
+    L.adaisp_unprocess.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, cu, vp]
+    L.adaisp_unprocess.restype = ci
     L.adaisp_nlm_general.argtypes = [vp, vp, vp, ci, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, vp]
     L.adaisp_nlm_general.restype = ci
     L.adaisp_nlm_general_workspace_bytes.argtypes = [ci, ci, ci]
@@ -288,6 +293,37 @@ def demosaic(raw, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None
         rc = L.adaisp_demosaic(raw.data_ptr(), out.data_ptr(), B, H, W, pat, float(black_level), float(white_level),
                                _stream())
     _check(rc, "adaisp_demosaic")
+    _wrote(out)
+    return out
+
+
+# adaisp_unprocess_desc (include/adaisp.h): one 96-byte record per image
+UNPROCESS_DESC = np.dtype([("src_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"),
+                           ("serial", "<u8"), ("p", "<f4", (16,))], align=True)
+assert UNPROCESS_DESC.itemsize == 96
+
+
+def unprocess(src, desc, S, seed=0, flags=0, out=None):
+    """adaisp_unprocess: uint8 HWC BGR images packed in the device byte tensor `src` (any offset: a slice is fine) ->
+    planar fp32 [B,3,S,S], letterboxed by `desc` (B records of UNPROCESS_DESC as a device byte tensor). flags: 0 (u8 / 255),
+    UNP_UNPROCESS, UNP_UNPROCESS | UNP_NOISE. Raises on bad arguments before any device work."""
+    L = load()
+    for t, name in ((src, "src"), (desc, "desc")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AdaispError(f"unprocess: {name} must be a HIP device tensor (there is no CPU path)")
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise AdaispError(f"unprocess: {name} must be a contiguous uint8 tensor, got {t.dtype}")
+    if desc.numel() % UNPROCESS_DESC.itemsize:
+        raise AdaispError(f"unprocess: desc holds {desc.numel()} bytes, not a whole number of {UNPROCESS_DESC.itemsize}-byte records")
+    B, S = desc.numel() // UNPROCESS_DESC.itemsize, int(S)
+    if out is None:
+        out = torch.empty((max(B, 1), 3, max(S, 1), max(S, 1)), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (B, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
+        raise AdaispError(f"unprocess: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {src.device}")
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_unprocess(src.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, int(seed) & (2 ** 64 - 1),
+                                int(flags), _stream())
+    _check(rc, "adaisp_unprocess")
     _wrote(out)
     return out
 

@@ -379,9 +379,12 @@ class _GraphIteration:
 # stands in.
 # ---------------------------------------------------------------------------------------------------------------
 def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epochs=800, save_dir=None, sync_bn=False,
-                  detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None):
+                  detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
+                  add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
-    frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast."""
+    frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
+    `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
+    reference's unprocess options; rank r reads files[r::world]; `workers` decoding threads); None: SyntheticSource."""
     import random
 
     from .agent import Agent
@@ -412,6 +415,11 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
         detector = YoloTrainEngine(det, batch_size, H, W, device=device)
     if tune_cache:
         detector.autotune(cache=tune_cache, write=(rank == 0))
+    if source is None and data is not None:
+        from .data import ImageFolderSource
+        source = ImageFolderSource(data, H, device, data_name=data_name, add_noise=add_noise,
+                                   brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
+                                   seed=seed, rank=rank, world=world, workers=workers)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -437,6 +445,15 @@ def main(argv=None):
     ap.add_argument("--detector-ckpt", default=None, help="yolov3.pt (pickled reference module)")
     ap.add_argument("--isp-ckpt", default=None, help="ckpt-*.pth to resume from")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--data", default=None, help="image directory or .txt list to train on (default: synthetic images)")
+    ap.add_argument("--data-name", default="lod", choices=("lod", "coco"),
+                    help="lod: images / 255; coco: sRGB -> synthetic low-light linear RGB (unprocess_wo_mosaic)")
+    ap.add_argument("--add-noise", action="store_true", help="coco: shot + read noise")
+    ap.add_argument("--bri-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="coco: random brightness ratio in [LO, HI)")
+    ap.add_argument("--noise-level", type=float, default=None, help="coco: fixed shot noise (default: random)")
+    ap.add_argument("--use-linear", action="store_true", help="coco: shot noise uniform instead of log-uniform")
+    ap.add_argument("--data-workers", type=int, default=4, help="decoding threads per rank")
     ap.add_argument("--gpus", type=int, default=None, help="start this many ranks (one per GPU) under torch.distributed.run "
                     "as a child process; without it the process is one rank of whatever torchrun set up")
     a = ap.parse_args(argv)
@@ -472,7 +489,9 @@ def main(argv=None):
             raise SystemExit(f"adaptiveisp_amd.train: {world} ranks but only {torch.cuda.device_count()} device(s) visible")
         cache = os.path.join(os.path.dirname(os.path.abspath(__file__)), "yolo", "tuning", "mi355x.json")
         tr = build_trainer(cfg, rank, world, device, a.batch, a.size, lr=a.lr, epochs=a.epochs, save_dir=a.save_dir,
-                           sync_bn=a.sync_bn, detector_ckpt=a.detector_ckpt, isp_ckpt=a.isp_ckpt, seed=a.seed, tune_cache=cache)
+                           sync_bn=a.sync_bn, detector_ckpt=a.detector_ckpt, isp_ckpt=a.isp_ckpt, seed=a.seed, tune_cache=cache,
+                           data=a.data, data_name=a.data_name, add_noise=a.add_noise, brightness_range=a.bri_range,
+                           noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers)
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 
@@ -514,6 +533,8 @@ def main(argv=None):
             for _ in range(reps):
                 torch.distributed.all_reduce(bucket.flat)
             ar_ms = (time.perf_counter() - t1) / reps * 1e3
+    describe = getattr(getattr(getattr(tr, "replay", None), "dataset", None), "describe", None)
+    data_desc = "synthetic" if describe is None else describe()
     if rank == 0:
         last = tr.history[-1] if tr.history else {}
         ms_it = dt / max(timed, 1) * 1e3
@@ -523,7 +544,7 @@ def main(argv=None):
                           "unit": "images/sec", "n_gpus": world, "steps": timed, "warmup": min(a.warmup, n),
                           "ms_per_step": round(ms_it, 2), "iterations_per_sec": round(1e3 / ms_it, 2) if timed else None,
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                          "dtype": "bf16 detector / fp32 ISP + heads", "data": "synthetic" + (" (DRY REHEARSAL: no device)" if dry else
+                          "dtype": "bf16 detector / fp32 ISP + heads", "data": data_desc + (" (DRY REHEARSAL: no device)" if dry else
                                                  " (REHEARSAL: all ranks share one device over gloo; not a measurement)"
                                                  if os.environ.get("ADAISP_DP_REHEARSAL") == "1" and world > 1 else ""),
                           "iters": timed, "ms_per_iter": round(ms_it, 2),

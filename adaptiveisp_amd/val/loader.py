@@ -145,6 +145,47 @@ def read_labels(path):
     return lb
 
 
+def load_letterboxed(path, img_size):
+    """The decode / geometry / label part of one letterboxed sample (auto=False, scaleup=False), shared by LODImages and
+    the training source (adaptiveisp_amd/data.py): load_image, then letterbox's resize to the un-padded size (only on a
+    ceil overshoot of load_image) WITHOUT the padding. Returns
+        (im HWC BGR uint8 un-padded, (top, left) of it in the frame, (H, W) of the frame, labels [k,5] class + xywh
+         normalised to the frame, shapes = ((h0, w0), ((h/h0, w/w0), (dw, dh))))."""
+    im, (h0, w0), (h, w) = load_image(path, img_size, augment=False)
+    ratio, new_unpad, pad, (top, bottom, left, right) = letterbox_geometry(im.shape[:2], img_size, False, False, False, 32)
+    if (im.shape[1], im.shape[0]) != tuple(new_unpad):
+        im = resize_linear_u8(im, new_unpad)
+    H, W = im.shape[0] + top + bottom, im.shape[1] + left + right
+    shapes = (h0, w0), ((h / h0, w / w0), pad)
+    lb = read_labels(_label_path(path)).copy()
+    if lb.size:                                   # normalised xywh (native) -> pixels in the letterboxed frame -> normalised
+        cx, cy = lb[:, 1] * (ratio[0] * w) + pad[0], lb[:, 2] * (ratio[1] * h) + pad[1]
+        bw, bh = lb[:, 3] * (ratio[0] * w), lb[:, 4] * (ratio[1] * h)
+        x1, y1, x2, y2 = cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2
+        x1, x2 = np.clip(x1, 0, W - 1e-3), np.clip(x2, 0, W - 1e-3)
+        y1, y2 = np.clip(y1, 0, H - 1e-3), np.clip(y2, 0, H - 1e-3)
+        lb[:, 1], lb[:, 2] = (x1 + x2) / 2 / W, (y1 + y2) / 2 / H
+        lb[:, 3], lb[:, 4] = (x2 - x1) / W, (y2 - y1) / H
+    return np.ascontiguousarray(im), (top, left), (H, W), lb, shapes
+
+
+def list_images(source):
+    """A directory (recursive), a .txt list (`./` entries relative to it) or a list of paths -> the image files, in the
+    order given (directories: sorted)."""
+    if isinstance(source, (list, tuple)):
+        files = list(source)
+    elif os.path.isdir(source):
+        files = sorted(glob.glob(os.path.join(source, "**", "*.*"), recursive=True))
+    else:
+        base = os.path.dirname(source)
+        files = [ln.strip() for ln in open(source) if ln.strip()]
+        files = [os.path.join(base, f[2:]) if f.startswith("./") else f for f in files]
+    files = [f for f in files if f.rsplit(".", 1)[-1].lower() in IMG_FORMATS]
+    if not files:
+        raise FileNotFoundError(f"no images under {source}")
+    return files
+
+
 class LODImages:
     """Iterates a dataset the way the evaluation of val_adaptiveisp.py sees it (rect=False, augment=False, pad 0):
     every image is scaled so its longer side is `img_size`, letterboxed to img_size x img_size with a BLACK border
@@ -153,17 +194,7 @@ class LODImages:
     with shapes[i] = ((h0, w0), ((h/h0, w/w0), (dw, dh))) — what `scale_boxes` needs to map boxes back."""
 
     def __init__(self, source, img_size=512, batch_size=1, device="cpu"):
-        if isinstance(source, (list, tuple)):
-            files = list(source)
-        elif os.path.isdir(source):
-            files = sorted(glob.glob(os.path.join(source, "**", "*.*"), recursive=True))
-        else:
-            base = os.path.dirname(source)
-            files = [ln.strip() for ln in open(source) if ln.strip()]
-            files = [os.path.join(base, f[2:]) if f.startswith("./") else f for f in files]
-        self.files = [f for f in files if f.rsplit(".", 1)[-1].lower() in IMG_FORMATS]
-        if not self.files:
-            raise FileNotFoundError(f"no images under {source}")
+        self.files = list_images(source)
         self.img_size, self.batch_size, self.device = int(img_size), int(batch_size), device
 
     def __len__(self):
@@ -171,20 +202,10 @@ class LODImages:
 
     def item(self, i):
         path = self.files[i]
-        im, (h0, w0), (h, w) = load_image(path, self.img_size, augment=False)
-        im, ratio, pad = letterbox(im, self.img_size, color=(0, 0, 0), auto=False, scaleup=False)
-        shapes = (h0, w0), ((h / h0, w / w0), pad)
-        lb = read_labels(_label_path(path)).copy()
-        if lb.size:                                   # normalised xywh (native) -> pixels in the letterboxed frame -> normalised
-            cx, cy = lb[:, 1] * (ratio[0] * w) + pad[0], lb[:, 2] * (ratio[1] * h) + pad[1]
-            bw, bh = lb[:, 3] * (ratio[0] * w), lb[:, 4] * (ratio[1] * h)
-            x1, y1, x2, y2 = cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2
-            H, W = im.shape[:2]
-            x1, x2 = np.clip(x1, 0, W - 1e-3), np.clip(x2, 0, W - 1e-3)
-            y1, y2 = np.clip(y1, 0, H - 1e-3), np.clip(y2, 0, H - 1e-3)
-            lb[:, 1], lb[:, 2] = (x1 + x2) / 2 / W, (y1 + y2) / 2 / H
-            lb[:, 3], lb[:, 4] = (x2 - x1) / W, (y2 - y1) / H
-        chw = np.ascontiguousarray(im.transpose(2, 0, 1)[::-1])          # HWC BGR -> CHW RGB
+        im, (top, left), (H, W), lb, shapes = load_letterboxed(path, self.img_size)
+        out = np.zeros((H, W, im.shape[2]), np.uint8)                    # letterbox(color=(0, 0, 0))
+        out[top:top + im.shape[0], left:left + im.shape[1]] = im
+        chw = np.ascontiguousarray(out.transpose(2, 0, 1)[::-1])         # HWC BGR -> CHW RGB
         return torch.from_numpy(chw).float() / 255.0, lb, path, shapes
 
     def __iter__(self):

@@ -145,6 +145,37 @@ int adaisp_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pa
                     float black_level, float white_level, void* stream);
 
 /*
+ * Replay-pool input conversion: decoded images -> the [B,3,S,S] fp32 letterboxed batch the RL trainer stores
+ * (the reference's `lod` and `coco` loaders, replay_memory.py:60-97).
+ * src: uint8 HWC BGR pixels (cv2.imread order) of every image, packed at any byte offsets. desc: a DEVICE array of B
+ * records; image b is desc[b].h x desc[b].w pixels at src + desc[b].src_offset, placed at (top, left) of its S x S
+ * output; every other output sample is exactly 0 (a placement that does not fit the frame gives an all-zero image).
+ *   flags 0                 convert: out = float(u8) / 255 (LoadImagesAndLabelsNormalizeReplay, dataset.py:794-897)
+ *   ADAISP_UNP_UNPROCESS    unprocess_wo_mosaic, isp/unprocess_np.py:248-292 (dataset.py:458-471), in fp32, with the
+ *                           per-image parameters p[] below (the random draws are the caller's)
+ *   | ADAISP_UNP_NOISE      + shot / read noise, :177-181 and the clip after it. The normals come from Philox4x32-10
+ *                           keyed by (seed, desc[b].serial), counter = the pixel's index in the un-padded image
+ *                           (Box-Muller): they depend on (seed, serial) only, not on the batch, position or offset.
+ * No allocation, no host synchronisation: capturable in a hipGraph. B <= 65535, S <= 32768.
+ */
+#define ADAISP_UNP_UNPROCESS 1u
+#define ADAISP_UNP_NOISE 2u
+#define ADAISP_UNP_CCM 0       /* p[0..8]: rgb2cam, row-major (apply_ccm: out_c = sum_k rgb2cam[c][k] in_k)      */
+#define ADAISP_UNP_GAIN 9      /* p[9..11]: (1/red_gain, 1, 1/blue_gain) / rgb_gain (safe_invert_gains)          */
+#define ADAISP_UNP_PRESCALE 12 /* p[12]: brightness before the inverse tone curve (the reference: 0.9)           */
+#define ADAISP_UNP_RATIO 13    /* p[13]: brightness ratio after the clip (adjust_random_brightness; 1 if none)  */
+#define ADAISP_UNP_SHOT 14     /* p[14], p[15]: shot and read noise (variance = x * shot + read)                 */
+#define ADAISP_UNP_READ 15
+typedef struct adaisp_unprocess_desc {
+    int64_t src_offset;        /* byte offset of the image's first pixel in src                                  */
+    int32_t h, w, top, left;   /* un-padded size and its placement in the S x S frame                            */
+    uint64_t serial;           /* noise key (with the seed)                                                      */
+    float p[16];               /* ADAISP_UNP_* slots (ignored by the convert mode)                               */
+} adaisp_unprocess_desc;
+int adaisp_unprocess(const uint8_t* src, const adaisp_unprocess_desc* desc, float* out, int B, int S,
+                     uint64_t seed, unsigned flags, void* stream);
+
+/*
  * NonLocalMeansGray(search_window_size, patch_size).forward(rgb, h) for ANY odd sizes — isp/denoise.py:93-119 (class default
  * 21 / 7; the ISP's DenoiseFilter constructs 11 / 5, isp/filters.py:577, which ADAISP_OP_NLM serves with the tuned kernel).
  * Luminance 0.299 R + 0.587 G + 0.114 B of the CLIPPED image (rgb_to_luminance :11-17), patch distance = box sum of squared
