@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -65,6 +65,8 @@ def load():
     L.adaisp_demosaic.restype = ci
     L.adaisp_unprocess.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, cu, vp]
     L.adaisp_unprocess.restype = ci
+    L.adaisp_export_u8.argtypes = [vp, vp, ci, ci, ci, vp]
+    L.adaisp_export_u8.restype = ci
     L.adaisp_nlm_general.argtypes = [vp, vp, vp, ci, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, vp]
     L.adaisp_nlm_general.restype = ci
     L.adaisp_nlm_general_workspace_bytes.argtypes = [ci, ci, ci]
@@ -324,6 +326,26 @@ def unprocess(src, desc, S, seed=0, flags=0, out=None):
         rc = L.adaisp_unprocess(src.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, int(seed) & (2 ** 64 - 1),
                                 int(flags), _stream())
     _check(rc, "adaisp_unprocess")
+    _wrote(out)
+    return out
+
+
+def export_u8(img, out=None):
+    """adaisp_export_u8: planar fp32 RGB [B,3,H,W] on the device -> uint8 HWC BGR [B,H,W,3] on the device, the bytes the
+    reference's save_img gives cv2.imwrite (NaN -> 0, clip to [0, 1], * 255 in fp32, round half to even). `out`: any
+    uint8 [B,H,W,3] device tensor, contiguous (a view at any byte offset is fine). Raises on bad arguments before any
+    device work."""
+    L = load()
+    img = _dev_f32(img.detach(), "img")
+    B, H, W = _img_shape(img)
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=img.device)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8
+          or not out.is_contiguous() or out.device != img.device):
+        raise AdaispError(f"export_u8: out must be a contiguous uint8 [{B},{H},{W},3] tensor on {img.device}")
+    with torch.cuda.device(img.device):
+        rc = L.adaisp_export_u8(img.data_ptr(), out.data_ptr(), B, H, W, _stream())
+    _check(rc, "adaisp_export_u8")
     _wrote(out)
     return out
 

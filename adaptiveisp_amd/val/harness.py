@@ -8,6 +8,7 @@ import os
 import numpy as np
 import torch
 
+from .. import _lib
 from ..util import STATE_STOPPED_DIM
 from .boxes import scale_boxes, xywh2xyxy
 from .metrics import ap_per_class, process_batch
@@ -115,14 +116,23 @@ class _EpisodeGraph:
 
 
 def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False,
-             pipeline=None, records_path=None, nc=80, nms_fn=None, param_dir=None, details=None, graph=False):
+             pipeline=None, records_path=None, nc=80, nms_fn=None, param_dir=None, details=None, graph=False,
+             image_dir=None, image_writer=None, on_image=None):
     """Returns dict(mp, mr, map50, map75, map, seen, nt, ap_class, ap, records). `detector(x)` -> [B, N, 5+nc]
     decoded predictions (YoloEngine or the module tree in eval mode). `pipeline`: optional list of forced filter ids
     per step (val_adaptiveisp.py:292, --pipeline). `param_dir`: write one JSON per batch (named after its first image) with
     the chosen filter ids and image 0's regressed parameters per step, as `--save_param` does (:296-301,324-327).
     `details`: a list that receives one dict per image (path, retouched image, detections after NMS, `correct` matrix).
     `graph`: replay each batch's ISP episode + detector forward as one hipGraph (captured once per batch shape; HIP device,
-    eval-mode agent, no `param_dir`) — same records, detections and mAP as the eager loop, which stays the default."""
+    eval-mode agent, no `param_dir`) — same records, detections and mAP as the eager loop, which stays the default.
+    `image_dir`: write every image's retouched result after each step that ran as image_dir/step-<i>/<file name> (the step
+    directories are created as the steps run), as
+    `--save_image` does (:312-318, without its read past the last step of an early exit): per step one adaisp_export_u8
+    launch and one device-to-host copy of uint8 BGR, encoded on `image_writer` (a val.writers.ImageWriter; default: one of
+    its own, joined before returning). The eager loop then runs even with `graph`: the replay keeps no per-step images.
+    `on_image(path, predn, shape)`: called for every image with detections, with them in native image space (xyxy, conf,
+    class; a host tensor) and its native (h, w): where the reference saves --save-txt / --save-json (:371-374).
+    The result also holds per-class precision `p` and recall `r` (rows in `ap_class` order)."""
     import collections
     import json
     from ..util import get_initial_states, get_noise, to_device_async
@@ -132,6 +142,10 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
     stats, records, seen = [], [], 0
     graphs = {}
     filter_names = [f.get_short_name() for f in agent.filters]
+    own_writer = None
+    if image_dir is not None and image_writer is None:
+        from .writers import ImageWriter
+        image_writer = own_writer = ImageWriter()
     def front(batch):
         """Uploads + the ISP episode + the detector forward of one batch: eagerly, or (graph=True) as an asynchronous replay."""
         im, targets, paths, shapes = batch
@@ -145,7 +159,7 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
         noises = to_device_async(np.array([get_noise(nb, cfg.z_type, cfg.z_dim) for _ in range(steps)]), dev)
         states = to_device_async(get_initial_states(nb, cfg.num_state_dim, len(agent.filters)), dev)
         ctx = dict(im=im, targets=targets, paths=paths, shapes=shapes, noises=noises, states=states, nb=nb, slot=None)
-        if graph and im.is_cuda and not param_dir and not agent.training:
+        if graph and im.is_cuda and not param_dir and image_dir is None and not agent.training:
             key = (tuple(im.shape), steps, None if pipeline is None else tuple(pipeline))
             eg = graphs.get(key)
             if eg is None:
@@ -175,11 +189,22 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
             for i in range(0 if not replayed else steps, steps):
                 pipe = None if pipeline is None else pipeline[i]
                 (retouch, states, _, _), dbg, _ = agent((retouch, noises[i], states), 1.0, None, pipe)
+                if image_dir is not None:
+                    # the step's image as uint8 BGR, copied into pinned memory behind the export: the host read below
+                    # waits for it on the same stream
+                    u8 = _lib.export_u8(retouch)
+                    step_u8 = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+                    step_u8.copy_(u8, non_blocking=True)
                 # the step's two host reads — the chosen filter ids (records.txt) and image 0's "stopped" state (the early
                 # exit below, val_adaptiveisp.py:302-303) — in ONE device-to-host copy: the loop is host-bound at batch 1
                 host = torch.cat([dbg["selected_filter"].detach().to(torch.float32),
                                   states[0:1, STATE_STOPPED_DIM].detach().to(torch.float32)]).cpu().tolist()
                 ids.append([int(v) for v in host[:-1]])
+                if image_dir is not None:
+                    os.makedirs(os.path.join(image_dir, f"step-{i}"), exist_ok=True)
+                    for b in range(nb):
+                        image_writer.submit(os.path.join(image_dir, f"step-{i}", os.path.split(str(paths[b]))[1]),
+                                            step_u8[b].numpy())
                 if param_dir:
                     k = ids[-1][0]
                     params[filter_names[k]] = dbg["filter_debug_info"][k]["filter_parameters"].detach().cpu().numpy().tolist()
@@ -224,6 +249,8 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
                 correct = process_batch(predn, labelsn, iouv)
             if details is not None:
                 details[-1]["correct"] = correct.detach().cpu()
+            if on_image is not None:
+                on_image(str(paths[si]), predn.detach().cpu(), shape)
             stats.append((correct, pred[:, 4], pred[:, 5], labels[:, 0]))
         if slot is not None:
             _EpisodeGraph.release(slot)
@@ -231,20 +258,26 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
     # Graph mode is a two-stage pipeline over the batches: the replay of batch i + 1 (a side stream) runs while the host works
     # through NMS / matching of batch i (round 6: at batch 1 the loop was 1.8 ms of replay + 2.4 ms of host-bound NMS and matching
     # per image, one after the other). The eager loop keeps the reference's order: one batch at a time.
-    pending = None
-    for batch in batches:
-        ctx = front(batch)
+    pending, finished = None, False
+    try:
+        for batch in batches:
+            ctx = front(batch)
+            if pending is not None:
+                back(pending)
+                pending = None
+            if ctx["slot"] is not None:
+                pending = ctx
+            else:
+                back(ctx)
         if pending is not None:
             back(pending)
-            pending = None
-        if ctx["slot"] is not None:
-            pending = ctx
-        else:
-            back(ctx)
-    if pending is not None:
-        back(pending)
+        finished = True
+    finally:
+        # the writer's threads are joined on every path; a failed write is raised only when nothing else is in flight
+        if own_writer is not None:
+            own_writer.close(raise_errors=finished)
     res = dict(mp=0.0, mr=0.0, map50=0.0, map75=0.0, map=0.0, seen=seen, ap_class=np.zeros(0, int), ap=np.zeros((0, niou)),
-               records=records, filter_names=filter_names)
+               records=records, filter_names=filter_names, p=np.zeros(0), r=np.zeros(0))
     stats = [torch.cat(x, 0).cpu().numpy() for x in zip(*stats)] if stats else []
     # (the copy above drained the device) a persistent conv chain whose dependency wait gave up has produced wrong detections
     # with every launch returning OK: every forward polls the host word of the one before it, this covers the last one
@@ -253,7 +286,7 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
     if len(stats) and stats[0].any():
         tp, fp, p, r, f1, ap, ap_class = ap_per_class(*stats)
         res.update(mp=float(p.mean()), mr=float(r.mean()), map50=float(ap[:, 0].mean()), map75=float(ap[:, 5].mean()),
-                   map=float(ap.mean(1).mean()), ap=ap, ap_class=ap_class)
+                   map=float(ap.mean(1).mean()), ap=ap, ap_class=ap_class, p=p, r=r)
     res["nt"] = np.bincount(stats[3].astype(int), minlength=nc) if len(stats) else np.zeros(nc, int)
     if records_path:
         with open(records_path, "w") as f:                         # val_adaptiveisp.py:269-322 "records.txt"

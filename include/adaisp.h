@@ -176,6 +176,14 @@ int adaisp_unprocess(const uint8_t* src, const adaisp_unprocess_desc* desc, floa
                      uint64_t seed, unsigned flags, void* stream);
 
 /*
+ * Image export: planar fp32 RGB img [B,3,H,W] -> interleaved uint8 BGR out [B,H,W,3] (cv2.imwrite's channel order), in one
+ * launch, with the arithmetic of the reference's `save_img` (util.py:21-40) and OpenCV's float -> 8U conversion:
+ * NaN -> 0, clip to [0, 1], * 255.0f in fp32, round half to even. Any pointer alignment (16-byte loads where the
+ * alignment and H*W % 4 == 0 allow). No allocation, no host synchronisation. B <= 65535.
+ */
+int adaisp_export_u8(const float* img, uint8_t* out, int B, int H, int W, void* stream);
+
+/*
  * NonLocalMeansGray(search_window_size, patch_size).forward(rgb, h) for ANY odd sizes — isp/denoise.py:93-119 (class default
  * 21 / 7; the ISP's DenoiseFilter constructs 11 / 5, isp/filters.py:577, which ADAISP_OP_NLM serves with the tuned kernel).
  * Luminance 0.299 R + 0.587 G + 0.114 B of the CLIPPED image (rgb_to_luminance :11-17), patch distance = box sum of squared
