@@ -8,12 +8,16 @@ One "step" = one batch through the whole hot path with inputs resident in HBM:
 N GPUs = N independent replicas (one process per GPU, no data-path collective): scaling "weak".
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0). Extra objects: `roofline` (dominant kernel = the conv kernel with the largest total time,
-timed per launch with HIP events on the launch stream, inside the network, beside the ISP stream; the next three in `other_kernels`), `isp` (per-step ISP kernel times vs the HBM roof)
-and `cpu_baseline` (the reference's op chain restated on torch-CPU + plain torch-CPU detector on a bounded sample,
-host cores of this box; 1 warm-up + 3 repeats, min/median).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline
+keys only. --full adds everything else, each outside the timed region: `single_stream` and `device_selected_path` (the
+same steps launched other ways), `roofline` (dominant kernel = the conv kernel with the largest total time, timed per launch
+with HIP events on the launch stream, inside the network, beside the ISP stream; the next three in `other_kernels`), `isp`
+(per-step ISP kernel times vs the HBM roof), `h2d` and the other BASELINE configs (run_extras), and `cpu_baseline` (the
+reference's op chain restated on torch-CPU + plain torch-CPU detector on a bounded sample, host cores of this box; 1 warm-up
++ 3 repeats, min/median). --no-detail / --no-extras / --no-cpu-baseline leave parts of that out again.
 """
 import argparse
 import json
@@ -64,10 +68,14 @@ def parse():
                     "(build_interleaved; measured 0.12-0.15 ms per step SLOWER, tools/pipeline_points_ab.py)")
     ap.add_argument("--retune", action="store_true", help="re-measure the per-layer conv variants instead of loading "
                     "adaptiveisp_amd/yolo/tuning/*.json")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-detail", action="store_true", help="skip the per-kernel roofline passes")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra keys for BASELINE configs 3, 4, 5 (train_iteration, "
-                    "eval_config3, config5: ~1 minute, outside the timed region)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else the line can carry "
+                    "(other launch forms, per-kernel roofline, ISP kernels, h2d, BASELINE configs 3, 4, 5, cpu_baseline: "
+                    "~2 minutes, outside the timed region); a plain run prints the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-detail", action="store_true", help="with --full: skip the other launch forms, the per-kernel "
+                    "roofline passes and the extras")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip h2d and the extra keys for BASELINE configs 3, "
+                    "4, 5 (train_iteration, eval_config3, config5, batch16, raw: ~1 minute)")
     ap.add_argument("--cpu-probe", type=int, default=0, help=argparse.SUPPRESS)      # child of cpu_baseline (all-cores figure)
     ap.add_argument("--raw", action="store_true", help="start every step from a uint16 RGGB Bayer plane in HBM (adaisp_demosaic, "
                     "an extension: the reference's pipeline starts from RGB) instead of the fp32 RGB batch")
@@ -77,6 +85,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if not a.full:                                        # a plain run: nothing beyond the headline
+        a.no_detail = a.no_extras = a.no_cpu_baseline = True
     return a
 
 
@@ -1164,6 +1174,7 @@ def main():
         single_run = engine = x0 = step = None
         a.no_detail = a.no_cpu_baseline = True
     else:
+        mark("building the workload: engine, eager step, hipGraph capture")
         run, single_run, graphed, pipelined, engine, x0, sched, step = prepare_gpu_run(a, dev)
         Hp = engine.Hp
     mark("workload built; warm-up")

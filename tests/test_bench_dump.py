@@ -49,3 +49,15 @@ def test_steps_sets_the_timed_steps():
 def test_dump_outputs_refused_without_a_device(tmp_path):
     r = _bench("--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "d"))
     assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(tmp_path / "d")
+
+
+def test_plain_run_is_the_headline_and_full_adds_the_rest(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert not a.full and a.no_detail and a.no_extras and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extras"])
+    a = bench.parse()
+    assert a.full and not a.no_detail and a.no_extras and not a.no_cpu_baseline
+    r = _bench("--steps", "2", "--warmup", "0", "--full")
+    assert r.returncode == 0, r.stderr[-2000:]
