@@ -8,7 +8,7 @@
 // shuffles, the workgroup through LDS, then ONE float atomic per parameter per workgroup.
 // The stencil ops re-read their neighbourhood through L1/L2 (this is not the headline path);
 // NLM reuses the forward kernel's tile machinery (isp_nlm.hip, GRAD instantiation).
-#include "isp_internal.h"
+#include "isp_filter_math.h"
 
 namespace adaisp {
 namespace {
@@ -33,39 +33,6 @@ __device__ __forceinline__ void block_reduce_atomic(float (&g)[NG], float* __res
     }
 }
 
-__device__ __forceinline__ float gate01(float f, bool clip) { return (!clip || (f >= 0.0f && f <= 1.0f)) ? 1.0f : 0.0f; }
-__device__ __forceinline__ float lum276(float r, float g, float b) { return (0.27f * r + 0.67f * g) + 0.06f * b; }
-__device__ __forceinline__ float py_mod(float a, float m) {
-    float r = fmodf(a, m);
-    if (r != 0.0f && r < 0.0f) r += m;
-    return r;
-}
-
-// full-colour term of SaturationPlus (same arithmetic as the forward kernel)
-__device__ __forceinline__ void sat_full(float r, float g, float b, float& fr, float& fg, float& fb) {
-    const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b);
-    const float d = (mx - mn) + 1e-8f;
-    float hue = 0.0f;
-    if (b == mx) hue = 4.0f + (r - g) / d;
-    if (g == mx) hue = 2.0f + (b - r) / d;
-    if (r == mx) hue = py_mod((g - b) / d, 6.0f);
-    if (mn == mx) hue = 0.0f;
-    hue = hue / 6.0f;
-    float s = (mx - mn) / (mx + 1e-8f);
-    if (mx == 0.0f) s = 0.0f;
-    const float es = s + (1.0f - s) * (0.5f - fabsf(0.5f - mx)) * 0.8f;
-    const float h = py_mod(hue, 1.0f), s2 = clamp01(es), v2 = clamp01(mx);
-    const float h6 = h * 6.0f, hi = floorf(h6), f = h6 - hi;
-    const float pp = v2 * (1.0f - s2), qq = v2 * (1.0f - (f * s2)), tt = v2 * (1.0f - ((1.0f - f) * s2));
-    fr = fg = fb = 0.0f;
-    if (hi == 0.0f) { fr = v2; fg = tt; fb = pp; }
-    else if (hi == 1.0f) { fr = qq; fg = v2; fb = pp; }
-    else if (hi == 2.0f) { fr = pp; fg = v2; fb = tt; }
-    else if (hi == 3.0f) { fr = pp; fg = qq; fb = v2; }
-    else if (hi == 4.0f) { fr = tt; fg = pp; fb = v2; }
-    else if (hi == 5.0f) { fr = v2; fg = pp; fb = qq; }
-}
-
 // ---- pointwise ops ---------------------------------------------------------------------------------
 template <int OP, int NG>
 __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restrict__ go, const float* __restrict__ p,
@@ -74,10 +41,9 @@ __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restr
 #pragma unroll
     for (int k = 0; k < NG; ++k) g[k] = 0.0f;
     // per-image constants
-    float c0 = 0.f, rs[3] = {1.f, 1.f, 1.f}, S[3] = {1.f, 1.f, 1.f};
+    float c0 = 0.f, ccm[3][3], rs[3] = {1.f, 1.f, 1.f}, S[3] = {1.f, 1.f, 1.f};
     if (OP == ADAISP_OP_EXPOSURE) c0 = expf(p[0] * 0.6931471805599453f);
-    if (OP == ADAISP_OP_CCM)
-        for (int i = 0; i < 3; ++i) rs[i] = (p[3 * i] + p[3 * i + 1]) + p[3 * i + 2];
+    if (OP == ADAISP_OP_CCM) ccm_rows(p, ccm, rs);
     if (OP == ADAISP_OP_TONE) { float s = 0.f; for (int i = 0; i < 8; ++i) s += p[i]; S[0] = S[1] = S[2] = s + 1e-30f; }
     if (OP == ADAISP_OP_COLOR)
         for (int ch = 0; ch < 3; ++ch) { float s = 0.f; for (int i = 0; i < 8; ++i) s += p[3 * i + ch]; S[ch] = s + 1e-30f; }
@@ -92,6 +58,7 @@ __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restr
         } else if (OP == ADAISP_OP_GAMMA) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
+                // (known difference: powf here, the forward's pow_pos in isp_pointwise.hip)
                 const float m = fmaxf(x[c], 0.001f), f = powf(m, p[0]);
                 g[0] += go3[c] * gate01(f, clip) * f * logf(m);
             }
@@ -101,12 +68,13 @@ __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restr
         } else if (OP == ADAISP_OP_CCM) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float f = (x[0] * (p[3 * c] / rs[c]) + x[1] * (p[3 * c + 1] / rs[c])) + x[2] * (p[3 * c + 2] / rs[c]);
+                const float f = (x[0] * ccm[c][0] + x[1] * ccm[c][1]) + x[2] * ccm[c][2];
                 const float gg = go3[c] * gate01(f, clip) / rs[c];
 #pragma unroll
                 for (int j = 0; j < 3; ++j) g[3 * c + j] += gg * (x[j] - f);
             }
         } else if (OP == ADAISP_OP_TONE || OP == ADAISP_OP_COLOR) {
+            // a running sum over the segments: bit for bit the forward's CurveTable (see isp_pointwise.hip)
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 float t[8], acc = 0.0f;
@@ -121,7 +89,7 @@ __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restr
                 for (int j = 0; j < 8; ++j) g[OP == ADAISP_OP_TONE ? j : 3 * j + c] += gg * (t[j] - acc / S[c]);
             }
         } else if (OP == ADAISP_OP_CONTRAST) {
-            const float L = clamp01(lum276(x[0], x[1], x[2]));
+            const float L = clamp01(lum_27_67_06(x[0], x[1], x[2]));
             const float cl = -cosf(3.14159274101257324f * L) * 0.5f + 0.5f, den = L + 1e-6f;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -129,7 +97,7 @@ __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restr
                 g[0] += go3[c] * gate01(f, clip) * (ci - x[c]);
             }
         } else if (OP == ADAISP_OP_WNB) {
-            const float L = lum276(x[0], x[1], x[2]);
+            const float L = lum_27_67_06(x[0], x[1], x[2]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float f = (1.0f - p[0]) * x[c] + p[0] * L;
@@ -138,7 +106,7 @@ __device__ void bwd_pointwise(const float* __restrict__ in, const float* __restr
         } else if (OP == ADAISP_OP_SATPLUS) {
             const float xc[3] = {clamp01(x[0]), clamp01(x[1]), clamp01(x[2])};
             float fc[3];
-            sat_full(xc[0], xc[1], xc[2], fc[0], fc[1], fc[2]);
+            satplus_full(xc[0], xc[1], xc[2], fc[0], fc[1], fc[2]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float f = xc[c] * (1.0f - p[0]) + fc[c] * p[0];
@@ -174,12 +142,6 @@ __global__ __launch_bounds__(kThreads) void k_bwd_pointwise(const float* __restr
 }
 
 // ---- 3x3 sharpen pair and 5x5 unsharp mask ------------------------------------------------------------
-__device__ __forceinline__ int reflect(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i;
-}
-
 __global__ __launch_bounds__(kThreads) void k_bwd_conv(const float* __restrict__ img, const float* __restrict__ go,
                                                        const int32_t* __restrict__ ids, const float* __restrict__ params,
                                                        int pstride, float* __restrict__ gparams, int H, int W) {
@@ -195,12 +157,12 @@ __global__ __launch_bounds__(kThreads) void k_bwd_conv(const float* __restrict__
     float w5[5][5], dw5[5][5];
     if (op == ADAISP_OP_USM) {
         const float sg = p[0];
-        float g1[5], dg[5], S = 0.0f, dS = 0.0f;
+        float g1[5], dg[5], dS = 0.0f;
+        const float S = usm_gauss(sg, g1);
         for (int i = 0; i < 5; ++i) {
-            const float xi = (float)(i - 2), t = xi / sg;
-            g1[i] = expf(-0.5f * (t * t));
+            const float xi = (float)(i - 2);
             dg[i] = g1[i] * xi * xi / (sg * sg * sg);
-            S += g1[i]; dS += dg[i];
+            dS += dg[i];
         }
         for (int i = 0; i < 5; ++i)
             for (int j = 0; j < 5; ++j) {
@@ -225,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_conv(const float* __restrict__
                     dblur = fmaf(dw5[ii][jj], v, dblur);
                 }
             const float f = ctr + (ctr - blur) * p[1];
-            const float gt = gout * ((f >= 0.0f && f <= 1.0f) ? 1.0f : 0.0f);
+            const float gt = gout * in01(f);
             acc[0] += gt * (-p[1] * dblur);
             acc[1] += gt * (ctr - blur);
         } else {
@@ -237,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_conv(const float* __restrict__
                         blur = fmaf((ii == 1 && jj == 1) ? c13 : a13, src[(long)(y + ii - 1) * W + (x + jj - 1)], blur);
             }
             const float f = (op == ADAISP_OP_SHARPEN) ? ctr * p[0] + blur * (1.0f - p[0]) : ctr + (ctr - blur) * p[0];
-            acc[0] += gout * ((f >= 0.0f && f <= 1.0f) ? 1.0f : 0.0f) * (ctr - blur);
+            acc[0] += gout * in01(f) * (ctr - blur);
         }
     }
     block_reduce_atomic<2>(acc, gparams + (long)b * pstride);

@@ -14,20 +14,13 @@
 //   NLM (11x11 search, 5x5 patch): pass 1 recomputes the forward per pixel and writes a = g/W, b = -sum_c g_c N_c / W^2
 //                              to the workspace; pass 2 walks the 121 offsets over an LDS tile and gathers the colour and
 //                              patch-distance terms (see k_nlm_dimg).
-#include "isp_internal.h"
+#include "isp_filter_math.h"
 
 namespace adaisp {
 namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ float gate01(float f, bool clip) { return (!clip || (f >= 0.0f && f <= 1.0f)) ? 1.0f : 0.0f; }
-__device__ __forceinline__ float in01(float v) { return (v >= 0.0f && v <= 1.0f) ? 1.0f : 0.0f; }
-__device__ __forceinline__ float py_mod(float a, float m) {
-    float r = fmodf(a, m);
-    if (r != 0.0f && r < 0.0f) r += m;
-    return r;
-}
 __device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 // ---- pointwise ops -----------------------------------------------------------------------------------------------------
@@ -40,14 +33,14 @@ struct PwConst {
 __device__ __forceinline__ PwConst pw_const(int op, const float* __restrict__ p) {
     PwConst k{};
     if (op == ADAISP_OP_EXPOSURE) k.c0 = expf(p[0] * 0.6931471805599453f);
-    if (op == ADAISP_OP_CCM)
-        for (int i = 0; i < 3; ++i) {
-            const float rs = (p[3 * i] + p[3 * i + 1]) + p[3 * i + 2];
-            for (int j = 0; j < 3; ++j) k.m[i][j] = p[3 * i + j] / rs;
-        }
+    if (op == ADAISP_OP_CCM) {
+        float rs[3];
+        ccm_rows(p, k.m, rs);
+    }
     // The output gate of a pixel whose curve value lands on 1.0 depends on the last ulp of the curve's total, so the totals
     // are added in the order of the reference's reduction: running (tone, [B,8] contiguous: as the forward kernel) and, for
-    // the colour curves' strided [B,8,3] sum, four partial sums p[i] + p[i+4] folded in order.
+    // the colour curves' strided [B,8,3] sum, four partial sums p[i] + p[i+4] folded in order (known difference: the forward
+    // and the parameter gradient add each colour curve's total as one running sum).
     if (op == ADAISP_OP_TONE) {
         float s = 0.f;
         for (int i = 0; i < 8; ++i) s += p[i];
@@ -130,7 +123,8 @@ __device__ __forceinline__ void pw_grad(const float (&x)[3], const float (&go)[3
     } else if (OP == ADAISP_OP_GAMMA) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            // m^p on the hardware log2 / exp2 (~1 ulp each: the gradient, not the forward's bit pattern), m^(p-1) = m^p / m
+            // m^p on the hardware log2 / exp2 (~1 ulp each: the gradient, not the forward's bit pattern; a known difference from
+            // the forward's pow_pos and the parameter gradient's powf), m^(p-1) = m^p / m
             const float m = fmaxf(x[c], 0.001f);
             const float f = __builtin_amdgcn_exp2f(p[0] * __builtin_amdgcn_logf(m));
             dx[c] = x[c] >= 0.001f ? go[c] * gate01(f, clip) * (p[0] * f / m) : 0.0f;
@@ -161,7 +155,7 @@ __device__ __forceinline__ void pw_grad(const float (&x)[3], const float (&go)[3
             dx[c] = go[c] * gate01(acc * k.tsc[c], clip) * (slope * k.tsc[c]);
         }
     } else if (OP == ADAISP_OP_CONTRAST) {
-        const float L0 = (0.27f * x[0] + 0.67f * x[1]) + 0.06f * x[2];
+        const float L0 = lum_27_67_06(x[0], x[1], x[2]);
         const float L = clamp01(L0);
         const float cl = -cosf(3.14159274101257324f * L) * 0.5f + 0.5f, den = L + 1e-6f;
         const float a = p[0];
@@ -179,7 +173,7 @@ __device__ __forceinline__ void pw_grad(const float (&x)[3], const float (&go)[3
         dx[1] += gL * 0.67f;
         dx[2] += gL * 0.06f;
     } else if (OP == ADAISP_OP_WNB) {
-        const float L = (0.27f * x[0] + 0.67f * x[1]) + 0.06f * x[2];
+        const float L = lum_27_67_06(x[0], x[1], x[2]);
         const float a = p[0];
         float gs = 0.0f, gg[3];
 #pragma unroll
@@ -195,31 +189,7 @@ __device__ __forceinline__ void pw_grad(const float (&x)[3], const float (&go)[3
         if (clip) {
             const float xc[3] = {clamp01(x[0]), clamp01(x[1]), clamp01(x[2])};
             float fc[3];
-            // forward value for the output gate: the same arithmetic as the forward kernel
-            {
-                const float r = xc[0], g = xc[1], b = xc[2];
-                const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b);
-                const float d = (mx - mn) + 1e-8f;
-                float hue = 0.0f;
-                if (b == mx) hue = 4.0f + (r - g) / d;
-                if (g == mx) hue = 2.0f + (b - r) / d;
-                if (r == mx) hue = py_mod((g - b) / d, 6.0f);
-                if (mn == mx) hue = 0.0f;
-                hue = hue / 6.0f;
-                float s = (mx - mn) / (mx + 1e-8f);
-                if (mx == 0.0f) s = 0.0f;
-                const float es = s + (1.0f - s) * (0.5f - fabsf(0.5f - mx)) * 0.8f;
-                const float h = py_mod(hue, 1.0f), s2 = clamp01(es), v2 = clamp01(mx);
-                const float h6 = h * 6.0f, hi = floorf(h6), f = h6 - hi;
-                const float pp = v2 * (1.0f - s2), qq = v2 * (1.0f - (f * s2)), tt = v2 * (1.0f - ((1.0f - f) * s2));
-                fc[0] = fc[1] = fc[2] = 0.0f;
-                if (hi == 0.0f) { fc[0] = v2; fc[1] = tt; fc[2] = pp; }
-                else if (hi == 1.0f) { fc[0] = qq; fc[1] = v2; fc[2] = pp; }
-                else if (hi == 2.0f) { fc[0] = pp; fc[1] = v2; fc[2] = tt; }
-                else if (hi == 3.0f) { fc[0] = pp; fc[1] = qq; fc[2] = v2; }
-                else if (hi == 4.0f) { fc[0] = tt; fc[1] = pp; fc[2] = v2; }
-                else if (hi == 5.0f) { fc[0] = v2; fc[1] = pp; fc[2] = qq; }
-            }
+            satplus_full(xc[0], xc[1], xc[2], fc[0], fc[1], fc[2]);     // the forward value, for the output gate
 #pragma unroll
             for (int c = 0; c < 3; ++c) gg[c] *= in01(xc[c] * (1.0f - p[0]) + fc[c] * p[0]);
         }
@@ -301,12 +271,6 @@ __global__ __launch_bounds__(kThreads) void k_dimg_pointwise(const float* __rest
 // gradient also gathers around the mirrored coordinates (-q, 2n-2-q).
 constexpr int CTH = 16, CTW = 64;
 
-__device__ __forceinline__ int reflect(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i;
-}
-
 template <int R>
 __device__ void dimg_conv_tile(const float* __restrict__ in, const float* __restrict__ go, const float* __restrict__ p,
                                float* __restrict__ gi, int op, int H, int W, float* __restrict__ xs, float* __restrict__ gs) {
@@ -317,31 +281,7 @@ __device__ void dimg_conv_tile(const float* __restrict__ in, const float* __rest
     const long plane = (long)H * W;
 
     float w[2 * R + 1][2 * R + 1];
-    float amount;
-    if (R == 2) {      // USM weights exactly as the forward kernel forms them (isp_conv.hip)
-        const float sigma = p[0];
-        amount = p[1];
-        float g1[5], sum = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const float t = (float)(i - 2) / sigma;
-            g1[i] = expf(-0.5f * (t * t));
-            sum += g1[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) g1[i] = g1[i] / sum;
-#pragma unroll
-        for (int i = 0; i < 2 * R + 1; ++i)
-#pragma unroll
-            for (int j = 0; j < 2 * R + 1; ++j) w[i][j] = g1[i] * g1[j];
-    } else {
-        amount = p[0];
-        const float a = 1.0f / 13.0f, c5 = 5.0f / 13.0f;
-#pragma unroll
-        for (int i = 0; i < 2 * R + 1; ++i)
-#pragma unroll
-            for (int j = 0; j < 2 * R + 1; ++j) w[i][j] = (i == R && j == R) ? c5 : a;
-    }
+    const float amount = stencil_weights<R>(p, w);
 
     for (int c = 0; c < 3; ++c) {
         const float* src = in + c * plane;
@@ -470,11 +410,6 @@ __global__ __launch_bounds__(kThreads) void k_dimg_conv(const float* __restrict_
 constexpr int NSR = 5, NPR = 2;
 constexpr int NTH = 16, NTW = 64;
 
-__device__ __forceinline__ int wrapi(int v, int n) {
-    v %= n;
-    return v < 0 ? v + n : v;
-}
-
 // pass 1: a (3 planes) and b per pixel into ws[b][4][H][W]. Lane = one column x 4 rows of a 16 x 64 tile; the patch
 // distances are column sums of row sums, all in registers.
 __global__ __launch_bounds__(kThreads) void k_nlm_ab(const float* __restrict__ img, const float* __restrict__ go,
@@ -493,9 +428,9 @@ __global__ __launch_bounds__(kThreads) void k_nlm_ab(const float* __restrict__ i
     const int x0 = blockIdx.x * NTW, y0 = blockIdx.y * NTH, tid = threadIdx.x;
     for (int q = tid; q < YR * YC; q += kThreads) {
         const int ly = q / YC, lx = q - ly * YC;
-        const long g = (long)wrapi(y0 + ly - HY, H) * W + wrapi(x0 + lx - HY, W);
+        const long g = (long)wrap(y0 + ly - HY, H) * W + wrap(x0 + lx - HY, W);
         const float r = clamp01(in[g]), gg = clamp01(in[g + plane]), bb = clamp01(in[g + 2 * plane]);
-        ylds[q] = (0.299f * r + 0.587f * gg) + 0.114f * bb;
+        ylds[q] = nlm_luma(r, gg, bb);
         const int cy = ly - NPR, cx = lx - NPR;
         if (cy >= 0 && cy < CR && cx >= 0 && cx < CC) {
             clds[0][cy * CC + cx] = r;
@@ -605,9 +540,9 @@ __global__ __launch_bounds__(kNT2) void k_nlm_dimg(const float* __restrict__ img
     const int x0 = blockIdx.x * N2W, y0 = blockIdx.y * N2H, tid = threadIdx.x;
 
     for_region<YRS, YCS>([&](int q, int ly, int lx) {
-        const long g = (long)wrapi(y0 + ly - YO, H) * W + wrapi(x0 + lx - YO, W);
+        const long g = (long)wrap(y0 + ly - YO, H) * W + wrap(x0 + lx - YO, W);
         const float r = clamp01(in[g]), gg = clamp01(in[g + plane]), bb = clamp01(in[g + 2 * plane]);
-        Y[q] = (0.299f * r + 0.587f * gg) + 0.114f * bb;
+        Y[q] = nlm_luma(r, gg, bb);
         const int cy = ly - (YO - CO), cx = lx - (YO - CO);
         if (cy >= 0 && cy < CRS && cx >= 0 && cx < CCS) {
             C[cy * CCS + cx] = r;
@@ -616,7 +551,7 @@ __global__ __launch_bounds__(kNT2) void k_nlm_dimg(const float* __restrict__ img
         }
     });
     for_region<ARS, ACS>([&](int q, int ly, int lx) {
-        const long g = (long)wrapi(y0 + ly - AO, H) * W + wrapi(x0 + lx - AO, W);
+        const long g = (long)wrap(y0 + ly - AO, H) * W + wrap(x0 + lx - AO, W);
 #pragma unroll
         for (int k = 0; k < 4; ++k) AB[k * ARS * ACS + q] = ab[g + k * plane];
     });
@@ -683,9 +618,8 @@ __global__ __launch_bounds__(kNT2) void k_nlm_dimg(const float* __restrict__ img
         const int gy = y0 + ty0 + 8 * k;
         if (gy >= H) continue;
         const long i = (long)gy * W + gx;
-        const float lum[3] = {0.299f, 0.587f, 0.114f};
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) o[i + ch * plane] = in01(in[i + ch * plane]) * (dc[k][ch] + lum[ch] * dyacc[k]);
+        for (int ch = 0; ch < 3; ++ch) o[i + ch * plane] = in01(in[i + ch * plane]) * (dc[k][ch] + kNlmLuma[ch] * dyacc[k]);
     }
 }
 

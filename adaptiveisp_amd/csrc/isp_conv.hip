@@ -1,12 +1,12 @@
 // Small-stencil ISP filters for gfx950: the 3x3 sharpen pair (adjust_sharpness / sharpness) and
-// the 5x5 gaussian unsharp mask. LDS-staged 2-D tiles: a 256-thread workgroup owns a 64x32 output
-// tile; the tile plus halo of all three planes is staged once into LDS with 16-B global loads
-// (quad-aligned columns x0-4 .. x0+67), then every lane produces 4 px x 2 rows per plane and
-// stores 16 B per plane per row. HBM traffic stays at the algorithmic 24 B/px: halo re-reads of
-// neighbouring tiles are served by L2.
+// the 5x5 gaussian unsharp mask. Images whose rows are 16-byte aligned take the row-sliding walk
+// (k_conv_rows, below); any other shape takes LDS-staged 2-D tiles (k_conv): a 256-thread workgroup
+// owns a 64x32 output tile, the tile plus halo of all three planes (quad-aligned columns
+// x0-4 .. x0+67) is staged once into LDS pixel by pixel, then every lane produces 4 px x 2 rows
+// per plane. Halo re-reads of neighbouring tiles are served by L2.
 //
 // Reference: isp/sharpen.py:105-142 (adjust_sharpness), :145-182 (sharpness), :63-102 (unsharp_mask).
-#include "isp_internal.h"
+#include "isp_filter_math.h"
 
 #ifndef ISP_CONV_NT_LD
 #define ISP_CONV_NT_LD 0
@@ -23,14 +23,7 @@ constexpr int ROWS_MAX = TH + 2 * MAXR;
 
 enum Mode { kAdjust = 0, kSharpness = 1, kUSM = 2 };
 
-// torch 'reflect' padding index (edge not repeated); valid for -n < i < 2n-1.
-__device__ __forceinline__ int reflect(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i;
-}
-
-template <int R, int MODE, bool VEC>
+template <int R, int MODE>
 __device__ void conv_tile(float* __restrict__ lds, const float* __restrict__ in, float* __restrict__ out,
                           const float* __restrict__ p, int H, int W) {
     constexpr int ROWS = TH + 2 * R;
@@ -47,58 +40,27 @@ __device__ void conv_tile(float* __restrict__ lds, const float* __restrict__ in,
         int gy = y0 - R + ly;
         const int gx = x0 - 4 + 4 * lq;
         const float* src = in + c * plane;
-        float4 v;
         if (MODE == kUSM) gy = reflect(gy, H);
         const bool row_ok = (gy >= 0) && (gy < H);
-        if (VEC && row_ok && gx >= 0 && gx + 3 < W) {
-            v = *reinterpret_cast<const float4*>(src + (long)gy * W + gx);
-        } else {
-            float t[4];
+        float t[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int xx = gx + k;
-                if (MODE == kUSM) {
-                    // columns further than the reflect range (only in the unused part of the quad margin
-                    // or beyond the image's right edge of a partial tile) are never consumed
-                    xx = (xx > -W && xx < 2 * W - 1) ? reflect(xx, W) : 0;
-                    t[k] = row_ok ? src[(long)gy * W + xx] : 0.0f;
-                } else {
-                    t[k] = (row_ok && xx >= 0 && xx < W) ? src[(long)gy * W + xx] : 0.0f;
-                }
+        for (int k = 0; k < 4; ++k) {
+            int xx = gx + k;
+            if (MODE == kUSM) {
+                // columns further than the reflect range (only in the unused part of the quad margin
+                // or beyond the image's right edge of a partial tile) are never consumed
+                xx = (xx > -W && xx < 2 * W - 1) ? reflect(xx, W) : 0;
+                t[k] = row_ok ? src[(long)gy * W + xx] : 0.0f;
+            } else {
+                t[k] = (row_ok && xx >= 0 && xx < W) ? src[(long)gy * W + xx] : 0.0f;
             }
-            v = make_float4(t[0], t[1], t[2], t[3]);
         }
-        *reinterpret_cast<float4*>(lds + (c * ROWS + ly) * PITCH + 4 * lq) = v;
+        *reinterpret_cast<float4*>(lds + (c * ROWS + ly) * PITCH + 4 * lq) = make_float4(t[0], t[1], t[2], t[3]);
     }
 
     // ---- per-image weights ------------------------------------------------------------------------
     float w[2 * R + 1][2 * R + 1];
-    float amount;
-    if (MODE == kUSM) {
-        // _get_gaussian_kernel1d (isp/sharpen.py:15-23): pdf = exp(-0.5 * (x / sigma)^2), x = -2..2
-        const float sigma = p[0];
-        amount = p[1];
-        float g1[5], sum = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const float t = (float)(i - 2) / sigma;
-            g1[i] = expf(-0.5f * (t * t));
-            sum += g1[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) g1[i] = g1[i] / sum;
-#pragma unroll
-        for (int i = 0; i < 2 * R + 1; ++i)
-#pragma unroll
-            for (int j = 0; j < 2 * R + 1; ++j) w[i][j] = g1[i] * g1[j];
-    } else {
-        amount = p[0];
-        const float a = 1.0f / 13.0f, c5 = 5.0f / 13.0f;  // ones(3,3) with centre 5, divided by its sum
-#pragma unroll
-        for (int i = 0; i < 2 * R + 1; ++i)
-#pragma unroll
-            for (int j = 0; j < 2 * R + 1; ++j) w[i][j] = (i == R && j == R) ? c5 : a;
-    }
+    const float amount = stencil_weights<R>(p, w);
     __syncthreads();
 
     // ---- 4 px x 2 rows per lane per plane ---------------------------------------------------------
@@ -137,13 +99,9 @@ __device__ void conv_tile(float* __restrict__ lds, const float* __restrict__ in,
                 o[k] = clamp01(r);
             }
             float* dst = out + c * plane + (long)gy * W + gx;
-            if (VEC && gx + 3 < W) {
-                *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-            } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (gx + k < W) dst[k] = o[k];
-            }
+            for (int k = 0; k < 4; ++k)
+                if (gx + k < W) dst[k] = o[k];
         }
     }
 }
@@ -237,31 +195,7 @@ __device__ void conv_rows_core(const float* __restrict__ src, float* __restrict_
     const bool store_x = active && gx < x_store_end;
 
     float w[G][G];
-    float amount;
-    if (MODE == kUSM) {
-        const float sigma = p[0];
-        amount = p[1];
-        float g1[5], sum = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const float t = (float)(i - 2) / sigma;
-            g1[i] = expf(-0.5f * (t * t));
-            sum += g1[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) g1[i] = g1[i] / sum;
-#pragma unroll
-        for (int i = 0; i < G; ++i)
-#pragma unroll
-            for (int j = 0; j < G; ++j) w[i][j] = g1[i] * g1[j];
-    } else {
-        amount = p[0];
-        const float a = 1.0f / 13.0f, c5 = 5.0f / 13.0f;
-#pragma unroll
-        for (int i = 0; i < G; ++i)
-#pragma unroll
-            for (int j = 0; j < G; ++j) w[i][j] = (i == R && j == R) ? c5 : a;
-    }
+    const float amount = stencil_weights<R>(p, w);
 
     // ring of input rows: row (y_begin - R + n) lives in slot n % G
     float win[G][4 + 2 * R];
@@ -399,7 +333,6 @@ __global__ __launch_bounds__(64 * kPoolWaves) void k_conv_rows_pool(const float*
     }
 }
 
-template <bool VEC>
 __global__ __launch_bounds__(kThreads) void k_conv(const float* __restrict__ img, float* __restrict__ out,
                                                    const int32_t* __restrict__ ids, int uniform_op,
                                                    const float* __restrict__ params, int pstride, int H, int W) {
@@ -409,9 +342,9 @@ __global__ __launch_bounds__(kThreads) void k_conv(const float* __restrict__ img
     const long off = (long)b * 3 * H * W;
     const float* p = params + (long)b * pstride;
     switch (op) {
-        case ADAISP_OP_SHARPEN:    conv_tile<1, kAdjust, VEC>(lds, img + off, out + off, p, H, W); break;
-        case ADAISP_OP_SHARPEN_V2: conv_tile<1, kSharpness, VEC>(lds, img + off, out + off, p, H, W); break;
-        case ADAISP_OP_USM:        conv_tile<2, kUSM, VEC>(lds, img + off, out + off, p, H, W); break;
+        case ADAISP_OP_SHARPEN:    conv_tile<1, kAdjust>(lds, img + off, out + off, p, H, W); break;
+        case ADAISP_OP_SHARPEN_V2: conv_tile<1, kSharpness>(lds, img + off, out + off, p, H, W); break;
+        case ADAISP_OP_USM:        conv_tile<2, kUSM>(lds, img + off, out + off, p, H, W); break;
         default: break;
     }
 }
@@ -455,7 +388,7 @@ hipError_t launch_conv(const Batch& a, hipStream_t s) {
             hipLaunchKernelGGL((k_conv_rows<2, 1>), dim3(3 * strips, ((a.H + rs5 - 1) / rs5 + 3) / 4, a.B), dim3(kThreads), 0, s,
                                a.img, a.out, a.ids, a.uniform_op, a.params, a.pstride, a.H, a.W, strips, rs5);
     } else
-        hipLaunchKernelGGL(k_conv<false>, grid, dim3(kThreads), 0, s, a.img, a.out, a.ids, a.uniform_op, a.params,
+        hipLaunchKernelGGL(k_conv, grid, dim3(kThreads), 0, s, a.img, a.out, a.ids, a.uniform_op, a.params,
                            a.pstride, a.H, a.W);
     return hipGetLastError();
 }

@@ -20,7 +20,7 @@
 //
 // No barriers inside the 121-shift loop. Compute-bound on the fp32 VALU (≈3.3 kflop/px + 242
 // transcendentals per px), not on HBM (24 B/px).
-#include "isp_internal.h"
+#include "isp_filter_math.h"
 #ifndef NLM_FMA
 #define NLM_FMA 1             // k_nlm_fwd: column sums as fused multiply-add chains (round 4: 453.7 -> 438.4 us, -3.4 %; 0 = mul + add)
 #endif
@@ -56,11 +56,6 @@ __device__ __forceinline__ v2f pk_sub_bcast_hi(v2f a, v2f b) {     // plain: see
     return v2f{a.y, a.y} - b;
 }
 
-__device__ __forceinline__ int wrap(int v, int n) {
-    v %= n;
-    return v < 0 ? v + n : v;
-}
-
 // GRAD = false: forward (writes `out`). GRAD = true: d/dh of the forward, contracted with grad_out and summed over
 // the image: with w_s = exp(-d_s/hh), d w_s/dh = w_s d_s / hh^2 (h > 0), so
 //   d out_c/dh = (A_c - out_c * Bsum) / den,  A_c = sum_s x_sc w_s d_s / hh^2,  Bsum = sum_s w_s d_s / hh^2.
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void k_nlm(const float* __restrict__ img,
         const int gy = wrap(y0 + ly - HY, H), gx = wrap(x0 + lx - HY, W);
         const long g = (long)gy * W + gx;
         const float r = clamp01(in[g]), gg = clamp01(in[g + plane]), bb = clamp01(in[g + 2 * plane]);
-        const float yv = (0.299f * r + 0.587f * gg) + 0.114f * bb;     // denoise.py:17
+        const float yv = nlm_luma(r, gg, bb);
         reinterpret_cast<float*>(ylds2)[2 * q] = yv;                       // .x of row ly
         if (ly + 1 < YROWS) reinterpret_cast<float*>(ylds2)[2 * (q + YP) + 1] = yv;   // .y of row ly+1
         const int cy = ly - PR, cx = lx - PR;
@@ -287,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void k_nlm_sep(const float* __restrict__ 
         const int gy = wrap(y0 + ly - HY, H), gx = wrap(x0 - 2 - SR + lx, W);
         const long g = (long)gy * W + gx;
         const float r = clamp01(in[g]), gg = clamp01(in[g + plane]), bb = clamp01(in[g + 2 * plane]);
-        ylds[q] = (0.299f * r + 0.587f * gg) + 0.114f * bb;
+        ylds[q] = nlm_luma(r, gg, bb);
         const int cy = ly - PR;
         if (cy >= 0 && cy < CROWS) {
             clds[(0 * CROWS + cy) * SP + lx] = r;
@@ -472,7 +467,7 @@ __global__ __launch_bounds__(kThreads) void k_nlm_fwd(const float* __restrict__ 
             if (q >= YROWS * SP) break;
             const int ly = q / SP, lx = q - ly * SP;
             const float r = clamp01(rr[i]), gg = clamp01(gg4[i]), bb = clamp01(bb4[i]);
-            const float yv = (0.299f * r + 0.587f * gg) + 0.114f * bb;
+            const float yv = nlm_luma(r, gg, bb);
             if (ly < Y2ROWS) y2f[(ly * SP + lx) * 2] = yv;
             if (ly >= HALF) y2f[((ly - HALF) * SP + lx) * 2 + 1] = yv;
             const int cy = ly - PR;
@@ -677,7 +672,7 @@ __global__ __launch_bounds__(kThreads) void k_nlm_luma(const float* __restrict__
     const long b = i / plane, r = i - b * plane;
     const float* in = img + b * 3 * plane + r;
     const float rr = clamp01(in[0]), gg = clamp01(in[plane]), bb = clamp01(in[2 * plane]);
-    y[i] = (0.299f * rr + 0.587f * gg) + 0.114f * bb;
+    y[i] = nlm_luma(rr, gg, bb);
 }
 
 __global__ __launch_bounds__(kThreads) void k_nlm_general(const float* __restrict__ img, const float* __restrict__ ylum,

@@ -8,7 +8,7 @@
 //
 // Arithmetic follows the reference op order (compiled with -ffp-contract=off so that a*b+c stays
 // two roundings like the ATen mul/add chains it replaces). Reference: isp/filters.py.
-#include "isp_internal.h"
+#include "isp_filter_math.h"
 
 namespace adaisp {
 namespace {
@@ -43,6 +43,7 @@ __device__ __forceinline__ float pow_pos(float x, float g) {
     return fmaf(r, yl * 0.693147180559945309f, r);
 }
 
+// (known difference: the parameter gradient recomputes the power with powf, the image gradient as exp2(g * log2 x))
 struct OpGamma {  // isp/filters.py:244-245   pow(max(img, 0.001), gamma)
     float gm;
     __device__ void init(const float* p) { gm = p[0]; }
@@ -60,19 +61,15 @@ struct OpWB {  // isp/filters.py:271-272   img * gains
 };
 
 struct OpCCM {  // isp/filters.py:703-708,666-672   rows normalised by their sum, out[c] = sum_k img[k]*M[c][k]
-    float m[9];
+    float m[3][3];
     __device__ void init(const float* p) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float rs = (p[3 * i] + p[3 * i + 1]) + p[3 * i + 2];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) m[3 * i + j] = p[3 * i + j] / rs;
-        }
+        float rs[3];
+        ccm_rows(p, m, rs);
     }
     __device__ __forceinline__ void apply(float& r, float& g, float& b) const {
-        const float o0 = (r * m[0] + g * m[1]) + b * m[2];
-        const float o1 = (r * m[3] + g * m[4]) + b * m[5];
-        const float o2 = (r * m[6] + g * m[7]) + b * m[8];
+        const float o0 = (r * m[0][0] + g * m[0][1]) + b * m[0][2];
+        const float o1 = (r * m[1][0] + g * m[1][1]) + b * m[1][2];
+        const float o2 = (r * m[2][0] + g * m[2][1]) + b * m[2][2];
         r = o0; g = o1; b = o2;
     }
 };
@@ -150,10 +147,6 @@ template <class OP> struct OpSetup<OP, decltype((void)OP::kCurves)> {
     }
 };
 
-__device__ __forceinline__ float lum_27_67_06(float r, float g, float b) {  // isp/filters.py:12-14
-    return (0.27f * r + 0.67f * g) + 0.06f * b;
-}
-
 struct OpContrast {  // isp/filters.py:415-419
     float p0, q0;
     __device__ void init(const float* p) { p0 = p[0]; q0 = 1.0f - p[0]; }
@@ -176,47 +169,13 @@ struct OpWNB {  // isp/filters.py:435-437
     }
 };
 
-// torch.remainder for floats: result takes the sign of the divisor.
-__device__ __forceinline__ float py_mod(float a, float m) {
-    float r = fmodf(a, m);
-    if (r != 0.0f && (r < 0.0f)) r += m;   // m > 0 here
-    return r;
-}
-
-struct OpSatPlus {  // isp/filters.py:546-560 with rgb2hsv :445-478 and hsv2rgb :481-533
+struct OpSatPlus {  // isp/filters.py:546-560
     float p0, q0;
     __device__ void init(const float* p) { p0 = p[0]; q0 = 1.0f - p[0]; }
     __device__ __forceinline__ void apply(float& r_, float& g_, float& b_) const {
         const float r = clamp01(r_), g = clamp01(g_), b = clamp01(b_);
-        const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b);
-        const float d = (mx - mn) + 1e-8f;
-        // sequential masked overwrite: B branch, then G, then R (so ties resolve R > G > B), then grey
-        float hue = 0.0f;
-        if (b == mx) hue = 4.0f + (r - g) / d;
-        if (g == mx) hue = 2.0f + (b - r) / d;
-        if (r == mx) hue = py_mod((g - b) / d, 6.0f);
-        if (mn == mx) hue = 0.0f;
-        hue = hue / 6.0f;
-        float s = (mx - mn) / (mx + 1e-8f);
-        if (mx == 0.0f) s = 0.0f;
-        const float v = mx;
-        const float es = s + (1.0f - s) * (0.5f - fabsf(0.5f - v)) * 0.8f;
-        // hsv2rgb
-        const float h = py_mod(hue, 1.0f);
-        const float s2 = clamp01(es), v2 = clamp01(v);
-        const float h6 = h * 6.0f;
-        const float hi = floorf(h6);
-        const float f = h6 - hi;
-        const float pp = v2 * (1.0f - s2);
-        const float qq = v2 * (1.0f - (f * s2));
-        const float tt = v2 * (1.0f - ((1.0f - f) * s2));
-        float fr = 0.0f, fg = 0.0f, fb = 0.0f;
-        if (hi == 0.0f) { fr = v2; fg = tt; fb = pp; }
-        else if (hi == 1.0f) { fr = qq; fg = v2; fb = pp; }
-        else if (hi == 2.0f) { fr = pp; fg = v2; fb = tt; }
-        else if (hi == 3.0f) { fr = pp; fg = qq; fb = v2; }
-        else if (hi == 4.0f) { fr = tt; fg = pp; fb = v2; }
-        else if (hi == 5.0f) { fr = v2; fg = pp; fb = qq; }
+        float fr, fg, fb;
+        satplus_full(r, g, b, fr, fg, fb);
         r_ = r * q0 + fr * p0;
         g_ = g * q0 + fg * p0;
         b_ = b * q0 + fb * p0;
