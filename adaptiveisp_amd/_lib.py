@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_resize_u8", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -65,6 +65,9 @@ def load():
     L.adaisp_demosaic.restype = ci
     L.adaisp_unprocess.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, cu, vp]
     L.adaisp_unprocess.restype = ci
+    sz = ctypes.c_size_t
+    L.adaisp_resize_u8.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, ci, ci, vp]
+    L.adaisp_resize_u8.restype = ci
     L.adaisp_export_u8.argtypes = [vp, vp, ci, ci, ci, vp]
     L.adaisp_export_u8.restype = ci
     L.adaisp_nlm_general.argtypes = [vp, vp, vp, ci, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, vp]
@@ -328,6 +331,77 @@ def unprocess(src, desc, S, seed=0, flags=0, out=None):
     _check(rc, "adaisp_unprocess")
     _wrote(out)
     return out
+
+
+# adaisp_resize_desc (include/adaisp.h): one 56-byte record per image
+RESIZE_DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("tab_x", "<i8"), ("tab_y", "<i8"),
+                        ("src_h", "<i4"), ("src_w", "<i4"), ("dst_h", "<i4"), ("dst_w", "<i4"), ("mode", "<i4"),
+                        ("scale", "<f4")], align=True)
+assert RESIZE_DESC.itemsize == 56
+RESIZE_COPY, RESIZE_LINEAR, RESIZE_AREA_INT, RESIZE_AREA = 0, 1, 2, 3
+
+
+def _check_resize_records(records, src_bytes, dst_bytes, tab_words):
+    """What adaisp_resize_u8 would skip on the device is an error here: a mode, size or extent outside the buffers."""
+    r = records
+    if np.any((r["mode"] < RESIZE_COPY) | (r["mode"] > RESIZE_AREA)):
+        raise AdaispError(f"resize_u8: unknown mode in {sorted(set(r['mode'].tolist()))}")
+    for k in ("src_h", "src_w", "dst_h", "dst_w"):
+        if np.any((r[k] < 1) | (r[k] > 32768)):
+            raise AdaispError(f"resize_u8: {k} outside [1, 32768]")
+    sb = r["src_h"].astype(np.int64) * r["src_w"] * 3
+    db = r["dst_h"].astype(np.int64) * r["dst_w"] * 3
+    if np.any(r["src_offset"] < 0) or np.any(r["src_offset"] + sb > src_bytes):
+        raise AdaispError(f"resize_u8: a source image lies outside src ({src_bytes} bytes)")
+    if np.any(r["dst_offset"] < 0) or np.any(r["dst_offset"] + db > dst_bytes):
+        raise AdaispError(f"resize_u8: a destination image lies outside dst ({dst_bytes} bytes)")
+    same = (r["src_h"] == r["dst_h"]) & (r["src_w"] == r["dst_w"])
+    if np.any((r["mode"] == RESIZE_COPY) != same):
+        raise AdaispError("resize_u8: COPY is the mode of equal sizes, and only of them")
+    ai = r["mode"] == RESIZE_AREA_INT
+    if np.any(ai & ((r["src_w"] % r["dst_w"] != 0) | (r["src_h"] % r["dst_h"] != 0))):
+        raise AdaispError("resize_u8: AREA_INT needs integer factors")
+    tabbed = (r["mode"] == RESIZE_LINEAR) | (r["mode"] == RESIZE_AREA)
+    need = np.where(r["mode"] == RESIZE_LINEAR, 4, 1)           # LINEAR: 4 words per index; AREA: at least ptr[n + 1]
+    ends = np.maximum(r["tab_x"] + need * r["dst_w"] + (r["mode"] == RESIZE_AREA),
+                      r["tab_y"] + need * r["dst_h"] + (r["mode"] == RESIZE_AREA))
+    if np.any(tabbed & ((r["tab_x"] < 0) | (r["tab_y"] < 0) | (ends > tab_words))):
+        raise AdaispError(f"resize_u8: taps outside tabs ({tab_words} words)")
+
+
+def resize_u8(src, dst, desc, tabs, records):
+    """adaisp_resize_u8: uint8 HWC BGR images packed in the device byte tensor `src` -> `dst` (device bytes), image b
+    resampled as records[b] says (RESIZE_DESC: sizes, mode, byte offsets into src / dst, word offsets of its taps in
+    `tabs`). `desc` is the same records as a device byte tensor, `tabs` the taps (adaptiveisp_amd/resize.py) as a device
+    int32 tensor or a 4-byte aligned byte tensor, or None when no image needs taps. `records` (host) sizes the launch and
+    is checked against the buffers: raises on host tensors or malformed records before any device work. Capturable."""
+    L = load()
+    for t, name in ((src, "src"), (dst, "dst"), (desc, "desc")) + (() if tabs is None else ((tabs, "tabs"),)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AdaispError(f"resize_u8: {name} must be a HIP device tensor (there is no CPU path)")
+        if not t.is_contiguous():
+            raise AdaispError(f"resize_u8: {name} must be contiguous")
+    for t, name in ((src, "src"), (dst, "dst"), (desc, "desc")):
+        if t.dtype != torch.uint8:
+            raise AdaispError(f"resize_u8: {name} must be a uint8 tensor, got {t.dtype}")
+    if not isinstance(records, np.ndarray) or records.dtype != RESIZE_DESC or records.ndim != 1 or len(records) < 1:
+        raise AdaispError("resize_u8: records must be a non-empty 1-D numpy array of RESIZE_DESC")
+    if desc.numel() != records.nbytes:
+        raise AdaispError(f"resize_u8: desc holds {desc.numel()} bytes, records {records.nbytes}")
+    tab_words = 0
+    if tabs is not None:
+        if tabs.dtype not in (torch.uint8, torch.int32) or tabs.data_ptr() % 4 or (tabs.numel() * tabs.element_size()) % 4:
+            raise AdaispError("resize_u8: tabs must be int32 words (an int32 tensor or 4-byte aligned bytes)")
+        tab_words = tabs.numel() * tabs.element_size() // 4
+    _check_resize_records(records, src.numel(), dst.numel(), tab_words)
+    B = len(records)
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_resize_u8(src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(), desc.data_ptr(),
+                                None if tabs is None else tabs.data_ptr(), tab_words, B, int(records["dst_h"].max()),
+                                int(records["dst_w"].max()), _stream())
+    _check(rc, "adaisp_resize_u8")
+    _wrote(dst)
+    return dst
 
 
 def export_u8(img, out=None):

@@ -1,0 +1,177 @@
+// Replay-pool resampling (include/adaisp.h, adaisp_resize_u8): uint8 HWC BGR -> uint8 HWC BGR, per image one of
+//
+//   COPY       the bytes as they are
+//   LINEAR     resize_linear_u8 (adaptiveisp_amd/val/loader.py): int32 horizontal pass with the 11-bit taps of
+//              _linear_taps, then (((b0 * (t >> 4)) >> 16) + ((b1 * (b >> 4)) >> 16) + 2) >> 2, clip
+//   AREA_INT   resize_area_u8's integer-factor branch: integer block sum, (sum + 2) >> 2 for 2 x 2 blocks,
+//              rint(float(sum) * scale) otherwise
+//   AREA       resize_area_u8's general branch: t_i = sum_j wx_j * s_ij over the footprint's source columns, then
+//              sum_i wy_i * t_i over its source rows, each step one fp32 multiply then one fp32 add (no FMA: the build
+//              compiles with -ffp-contract=off and the steps are written __fmul_rn / __fadd_rn besides), source order,
+//              round half to even, clip
+//
+// Every weight comes from the host (adaptiveisp_amd/resize.py): the device recomputes nothing in floating point, so it
+// uses exactly the taps the host path uses.
+//
+// Mapping from the output side: a workgroup owns 256 consecutive pixels of one output row of one image
+// (grid = (ceil(max_w / 256), max_h, B)); a lane owns one output pixel with its 3 channels and reads the source bytes
+// it needs with byte loads, so images may start at any byte offset. The row's vertical taps are uniform across the
+// workgroup (scalar loads); a lane's horizontal taps are its own and stay in the L1 / L2 for the whole column.
+#include "isp_internal.h"
+
+static_assert(sizeof(adaisp_resize_desc) == 56, "adaisp_resize_desc is 56 bytes (adaptiveisp_amd/_lib.py)");
+
+namespace adaisp {
+namespace {
+
+constexpr int RS_THREADS = 256;
+constexpr int AREA_REG_TAPS = 16;   // horizontal AREA taps a lane keeps in registers (more: read from the table per row)
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)clampi(v, 0, 255); }
+
+// one CSR tap list of an AREA table: row `k` of `n` rows at word `base` of `tabs` (checked to fit by the caller)
+struct Csr {
+    const int32_t* idx;
+    const float* wt;
+    int lo, hi;
+};
+
+__device__ __forceinline__ Csr csr_row(const int32_t* __restrict__ tab, int n, int k) {
+    const int nnz = tab[n];
+    Csr r;
+    r.idx = tab + n + 1;
+    r.wt = reinterpret_cast<const float*>(tab + n + 1 + nnz);
+    r.lo = clampi(tab[k], 0, nnz);
+    r.hi = clampi(tab[k + 1], r.lo, nnz);
+    return r;
+}
+
+// an AREA table of n rows at word `base` lies inside tab_words (its nnz read only once the pointer array is known to fit)
+__device__ __forceinline__ bool csr_fits(const int32_t* __restrict__ tabs, int64_t base, int n, int64_t tab_words) {
+    if (base < 0 || base + n + 1 > tab_words) return false;
+    const int64_t nnz = tabs[base + n];
+    return nnz >= 0 && base + n + 1 + 2 * nnz <= tab_words;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void k_resize_u8(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                          uint8_t* __restrict__ dst, int64_t dst_bytes,
+                                                          const adaisp_resize_desc* __restrict__ desc,
+                                                          const int32_t* __restrict__ tabs, int64_t tab_words) {
+    const adaisp_resize_desc d = desc[blockIdx.z];
+    const int H = d.src_h, W = d.src_w, h = d.dst_h, w = d.dst_w;
+    const int y = blockIdx.y, x = blockIdx.x * RS_THREADS + threadIdx.x;
+    if (y >= h || x >= w) return;
+    // the whole image, source and destination, lies inside its buffers; otherwise nothing is written
+    if (H < 1 || W < 1 || H > 32768 || W > 32768 || h > 32768 || w > 32768 || d.src_offset < 0 || d.dst_offset < 0 ||
+        d.src_offset + (int64_t)H * W * 3 > src_bytes || d.dst_offset + (int64_t)h * w * 3 > dst_bytes)
+        return;
+    const uint8_t* __restrict__ s = src + d.src_offset;
+    uint8_t* __restrict__ o = dst + d.dst_offset + ((int64_t)y * w + x) * 3;
+    const int64_t rs = (int64_t)W * 3;                       // source row stride in bytes
+
+    if (d.mode == ADAISP_RESIZE_COPY) {
+        if (H != h || W != w) return;
+        const uint8_t* __restrict__ p = s + y * rs + x * 3;
+        o[0] = p[0];
+        o[1] = p[1];
+        o[2] = p[2];
+    } else if (d.mode == ADAISP_RESIZE_LINEAR) {
+        if (d.tab_x < 0 || d.tab_y < 0 || d.tab_x + 4 * (int64_t)w > tab_words || d.tab_y + 4 * (int64_t)h > tab_words)
+            return;
+        const int32_t* __restrict__ tx = tabs + d.tab_x;
+        const int32_t* __restrict__ ty = tabs + d.tab_y;
+        const int x0 = clampi(tx[x], 0, W - 1), x1 = clampi(tx[w + x], 0, W - 1), a0 = tx[2 * w + x], a1 = tx[3 * w + x];
+        const int y0 = clampi(ty[y], 0, H - 1), y1 = clampi(ty[h + y], 0, H - 1), b0 = ty[2 * h + y], b1 = ty[3 * h + y];
+        const uint8_t* __restrict__ r0 = s + y0 * rs;
+        const uint8_t* __restrict__ r1 = s + y1 * rs;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int top = (r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1) >> 4;
+            const int bot = (r1[x0 * 3 + c] * a0 + r1[x1 * 3 + c] * a1) >> 4;
+            o[c] = sat_u8((((b0 * top) >> 16) + ((b1 * bot) >> 16) + 2) >> 2);
+        }
+    } else if (d.mode == ADAISP_RESIZE_AREA_INT) {
+        if (W % w || H % h) return;
+        const int fx = W / w, fy = H / h;
+        int64_t sum[3] = {0, 0, 0};
+        for (int i = 0; i < fy; ++i) {
+            const uint8_t* __restrict__ p = s + (int64_t)(y * fy + i) * rs + (int64_t)x * fx * 3;
+            for (int j = 0; j < fx; ++j) {
+                sum[0] += p[3 * j];
+                sum[1] += p[3 * j + 1];
+                sum[2] += p[3 * j + 2];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            o[c] = (fx == 2 && fy == 2) ? (uint8_t)((sum[c] + 2) >> 2)
+                                        : sat_u8((int)rintf(__fmul_rn((float)sum[c], d.scale)));
+    } else if (d.mode == ADAISP_RESIZE_AREA) {
+        if (!csr_fits(tabs, d.tab_x, w, tab_words) || !csr_fits(tabs, d.tab_y, h, tab_words)) return;
+        const Csr cx = csr_row(tabs + d.tab_x, w, x);
+        const Csr cy = csr_row(tabs + d.tab_y, h, y);
+        const int nx = cx.hi - cx.lo;
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        if (nx <= AREA_REG_TAPS) {
+            // the lane's horizontal taps in registers, loaded once: every source row then costs only independent byte
+            // loads (shrink factors up to ~15 on the long side; 4032 -> 512 needs 9)
+            int xo[AREA_REG_TAPS];
+            float xw[AREA_REG_TAPS];
+#pragma unroll
+            for (int m = 0; m < AREA_REG_TAPS; ++m) {
+                xo[m] = m < nx ? clampi(cx.idx[cx.lo + m], 0, W - 1) * 3 : 0;
+                xw[m] = m < nx ? cx.wt[cx.lo + m] : 0.0f;
+            }
+            for (int k = cy.lo; k < cy.hi; ++k) {
+                const uint8_t* __restrict__ row = s + clampi(cy.idx[k], 0, H - 1) * rs;
+                const float wy = cy.wt[k];
+                float t[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int m = 0; m < AREA_REG_TAPS; ++m) {
+                    if (m < nx) {
+                        const uint8_t* __restrict__ p = row + xo[m];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) t[c] = __fadd_rn(t[c], __fmul_rn(xw[m], (float)p[c]));
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] = __fadd_rn(acc[c], __fmul_rn(wy, t[c]));
+            }
+        } else {
+            for (int k = cy.lo; k < cy.hi; ++k) {
+                const uint8_t* __restrict__ row = s + clampi(cy.idx[k], 0, H - 1) * rs;
+                const float wy = cy.wt[k];
+                float t[3] = {0.0f, 0.0f, 0.0f};
+                for (int m = cx.lo; m < cx.hi; ++m) {
+                    const uint8_t* __restrict__ p = row + clampi(cx.idx[m], 0, W - 1) * 3;
+                    const float wx = cx.wt[m];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) t[c] = __fadd_rn(t[c], __fmul_rn(wx, (float)p[c]));
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] = __fadd_rn(acc[c], __fmul_rn(wy, t[c]));
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = (uint8_t)fminf(fmaxf(rintf(acc[c]), 0.0f), 255.0f);
+    }
+}
+
+}  // namespace
+}  // namespace adaisp
+
+extern "C" int adaisp_resize_u8(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t dst_bytes,
+                                const adaisp_resize_desc* desc, const int32_t* tabs, size_t tab_words, int B, int max_h,
+                                int max_w, void* stream) {
+    using namespace adaisp;
+    if (!src || !dst || !desc || (!tabs && tab_words) || B < 1 || max_h < 1 || max_w < 1) return ADAISP_EINVAL;
+    if (B > 65535 || max_h > 32768 || max_w > 32768) return ADAISP_ESHAPE;   // grid.z, grid.y; 32-bit pixel indices
+    if (src_bytes > (size_t)INT64_MAX || dst_bytes > (size_t)INT64_MAX || tab_words > (size_t)INT64_MAX) return ADAISP_EINVAL;
+    const dim3 grid((unsigned)((max_w + RS_THREADS - 1) / RS_THREADS), (unsigned)max_h, (unsigned)B);
+    hipLaunchKernelGGL(k_resize_u8, grid, dim3(RS_THREADS), 0, static_cast<hipStream_t>(stream), src, (int64_t)src_bytes,
+                       dst, (int64_t)dst_bytes, desc, tabs ? tabs : reinterpret_cast<const int32_t*>(src),
+                       (int64_t)tab_words);
+    return hipGetLastError() == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+}

@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .val.loader import list_images, load_letterboxed
+from .val.loader import imread_bgr, letterboxed_geometry, letterboxed_labels, list_images, load_letterboxed
 
 # random_ccm's XYZ -> camera matrices and the sRGB RGB -> XYZ matrix (isp/unprocess_np.py:5-35; Brooks et al.,
 # "Unprocessing Images for Learned Raw Denoising", CVPR 2019)
@@ -96,16 +96,28 @@ class ImageFolderSource:
     the event of its previous copy has completed), issues one H2D copy of descriptors + pixels and one adaisp_unprocess
     launch on the current stream.
 
+    resize="device" (for photo-sized datasets): the worker threads only decode (and read the labels); the full-size uint8
+    image crosses PCIe, with the tap tables of adaptiveisp_amd/resize.py in the same copy, and adaisp_resize_u8 does
+    load_image's resample and, for the images whose ceil overshoots, letterbox's bilinear resample on the device, into a
+    device scratch that adaisp_unprocess then reads. Same bytes as the host path (the kernel reproduces val/loader.py's
+    arithmetic), same metadata draws and noise keys. HIP devices only.
+
     On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` has no CPU path and raises."""
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
-                 use_linear=False, seed=0, rank=0, world=1, workers=4):
+                 use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host"):
         if data_name not in ("lod", "coco"):
             raise ValueError(f"data_name must be 'lod' or 'coco', got {data_name!r}")
+        if resize not in ("host", "device"):
+            raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
         self.device = torch.device(device)
         if data_name == "coco" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(data_name='coco'): the unprocess runs on the HIP device only "
                                "(adaisp_unprocess); there is no CPU path")
+        if resize == "device" and self.device.type != "cuda":
+            raise RuntimeError("ImageFolderSource(resize='device'): the resample runs on the HIP device only "
+                               "(adaisp_resize_u8); there is no CPU path")
+        self.resize = resize
         if add_noise and data_name != "coco":
             raise ValueError("add_noise needs data_name='coco'")
         if brightness_range is not None and isinstance(brightness_range, (list, tuple)):
@@ -138,7 +150,7 @@ class ImageFolderSource:
 
     def describe(self):
         kind = "coco (unprocess" + (", noise" if self.add_noise else "") + ")" if self.data_name == "coco" else "lod"
-        return f"{kind}: {len(self.files)} files"
+        return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "")
 
     # ------------------------------------------------------------------------------------------------------ order
     def _next_index(self):
@@ -150,10 +162,21 @@ class ImageFolderSource:
         return i
 
     def _decode(self, i):
-        im, (top, left), _, lb, shapes = load_letterboxed(self.files[i], self.img_size)
+        """(im, top, left, label, path, shapes, sizes): with resize="device" `im` is the decoded image as it is and `sizes`
+        ((h, w) after load_image, (h2, w2) after letterbox's resize) says what the device makes of it; otherwise `im` is
+        load_letterboxed's and `sizes` None."""
+        path = self.files[i]
+        if self.resize == "device":
+            im = imread_bgr(path)
+            size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(im.shape[0], im.shape[1],
+                                                                                       self.img_size)
+            lb, sizes = letterboxed_labels(path, size, frame, ratio, pad), (size, unpad)
+        else:
+            im, (top, left), _, lb, shapes = load_letterboxed(path, self.img_size)
+            sizes = None
         label = np.zeros((len(lb), 6), np.float32)
         label[:, 1:] = lb
-        return im, top, left, label, self.files[i], shapes
+        return im, top, left, label, path, shapes, sizes
 
     def _take(self, n):
         """The next n decoded items; with workers, keeps up to 2 * n more decoding behind them."""
@@ -181,24 +204,71 @@ class ImageFolderSource:
             out[b, :, top:top + im.shape[0], left:left + im.shape[1]] = torch.from_numpy(chw).float() / 255.0
         return out.to(self.device)
 
+    def _resize_plan(self, items, head):
+        """Device resize: the byte layout after the unprocess descriptors (`head` bytes) and the two adaisp_resize_u8
+        calls. Staged (one H2D copy): descriptors of pass 1 / pass 2, their tap tables, the decoded images; after them,
+        device only: scratch 1 (load_image's resample of the images with r != 1) and scratch 2 (letterbox's resample of
+        the ceil overshoots, from scratch 1). Returns (layout dict, [(h, w, offset) of every final image relative to the
+        first decoded image])."""
+        from .resize import TapPlan
+        S = self.img_size
+        p1 = TapPlan()
+        sizes, pix = [], 0
+        for im, *_rest, (size, unpad) in items:
+            sizes.append((im.shape[:2], pix, size, unpad))
+            pix += im.size
+        off1, at1 = 0, {}
+        for b, (full, src_off, size, _unpad) in enumerate(sizes):
+            if tuple(size) != tuple(full):
+                p1.add(full, size, max(full) > S, src_off, off1)
+                at1[b] = off1
+                off1 += size[0] * size[1] * 3
+        p2 = TapPlan(base=p1.words)
+        off2, final = 0, []
+        for b, (full, src_off, size, unpad) in enumerate(sizes):
+            if tuple(unpad) != tuple(size):
+                p2.add(size, unpad, False, at1[b], off2)
+                final.append((unpad[0], unpad[1], pix + off1 + off2))
+                off2 += unpad[0] * unpad[1] * 3
+            elif b in at1:
+                final.append((size[0], size[1], pix + at1[b]))
+            else:
+                final.append((full[0], full[1], src_off))
+        rec1, rec2 = p1.descriptors(), p2.descriptors()
+        tab = np.concatenate([p1.table(), p2.table()])
+        r1 = head
+        r2 = r1 + (rec1.nbytes + 15) // 16 * 16
+        tb = r2 + (rec2.nbytes + 15) // 16 * 16
+        base = tb + (tab.nbytes + 15) // 16 * 16
+        lay = dict(rec1=rec1, rec2=rec2, tab=tab, r1=r1, r2=r2, tb=tb, base=base, s1=off1, s2=off2)
+        return lay, final
+
     def _device_batch(self, items):
         from . import _lib
         S, B = self.img_size, len(items)
         desc = np.zeros(B, _lib.UNPROCESS_DESC)
         dbytes = (B * _lib.UNPROCESS_DESC.itemsize + 15) // 16 * 16
-        off = 0
-        for b, (im, top, left, *_rest) in enumerate(items):
-            desc[b]["src_offset"], desc[b]["h"], desc[b]["w"] = off, im.shape[0], im.shape[1]
+        lay = None
+        if self.resize == "device":
+            lay, final = self._resize_plan(items, dbytes)
+        else:
+            final, off = [], 0
+            for im, *_rest in items:
+                final.append((im.shape[0], im.shape[1], off))
+                off += im.size
+        for b, ((h, w, src_offset), (im, top, left, *_rest)) in enumerate(zip(final, items)):
+            desc[b]["src_offset"], desc[b]["h"], desc[b]["w"] = src_offset, h, w
             desc[b]["top"], desc[b]["left"], desc[b]["serial"] = top, left, self.serial
             self.serial += 1
-            off += im.size
         flags = 0
         if self.data_name == "coco":
             flags = _lib.UNP_UNPROCESS | (_lib.UNP_NOISE if self.add_noise else 0)
             for b in range(B):
                 desc[b]["p"] = kernel_params(sample_unprocess_params(self.rs, self.add_noise, self.brightness_range,
                                                                      self.noise_level, self.use_linear))
-        total = dbytes + off
+        base = dbytes if lay is None else lay["base"]                   # where the staged pixels start
+        total = base + sum(it[0].size for it in items)
+        need = total if lay is None else total + lay["s1"] + lay["s2"]
         slot = self._slots[self._slot]
         self._slot = (self._slot + 1) % len(self._slots)
         if slot["event"] is not None:
@@ -207,14 +277,31 @@ class ImageFolderSource:
             slot["host"] = torch.empty(max(total, dbytes + B * S * S * 3), dtype=torch.uint8, pin_memory=True)
         host = slot["host"].numpy()
         host[:B * desc.itemsize] = desc.view(np.uint8)
-        pos = dbytes
+        if lay is not None:
+            for key, at in (("rec1", "r1"), ("rec2", "r2"), ("tab", "tb")):
+                host[lay[at]:lay[at] + lay[key].nbytes] = lay[key].view(np.uint8)
+        pos = base
         for im, *_rest in items:
             host[pos:pos + im.size] = im.reshape(-1)
             pos += im.size
         with torch.cuda.device(self.device):
-            if self._dev is None or self._dev.numel() < total:
-                self._dev = torch.empty(slot["host"].numel(), dtype=torch.uint8, device=self.device)
+            if self._dev is None or self._dev.numel() < need:
+                self._dev = torch.empty(max(slot["host"].numel(), need), dtype=torch.uint8, device=self.device)
             self._dev[:total].copy_(slot["host"][:total], non_blocking=True)
             slot["event"] = torch.cuda.Event()
             slot["event"].record()
-            return _lib.unprocess(self._dev[dbytes:total], self._dev[:B * desc.itemsize], S, seed=self.seed, flags=flags)
+            if lay is not None:
+                self._resize_on_device(lay, total)
+            return _lib.unprocess(self._dev[base:need], self._dev[:B * desc.itemsize], S, seed=self.seed, flags=flags)
+
+    def _resize_on_device(self, lay, total):
+        """The two adaisp_resize_u8 calls of a staged batch (see _resize_plan), on the current stream."""
+        from . import _lib
+        dev, s1, s2 = self._dev, lay["s1"], lay["s2"]
+        tabs = dev[lay["tb"]:lay["tb"] + lay["tab"].nbytes] if lay["tab"].size else None
+        if len(lay["rec1"]):
+            _lib.resize_u8(dev[lay["base"]:total], dev[total:total + s1], dev[lay["r1"]:lay["r1"] + lay["rec1"].nbytes],
+                           tabs, lay["rec1"])
+        if len(lay["rec2"]):
+            _lib.resize_u8(dev[total:total + s1], dev[total + s1:total + s1 + s2],
+                           dev[lay["r2"]:lay["r2"] + lay["rec2"].nbytes], tabs, lay["rec2"])

@@ -380,11 +380,12 @@ class _GraphIteration:
 # ---------------------------------------------------------------------------------------------------------------
 def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epochs=800, save_dir=None, sync_bn=False,
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
-                  add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4):
+                  add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host"):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
-    reference's unprocess options; rank r reads files[r::world]; `workers` decoding threads); None: SyntheticSource."""
+    reference's unprocess options; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
+    where the resample to the training size runs); None: SyntheticSource."""
     import random
 
     from .agent import Agent
@@ -419,7 +420,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
         from .data import ImageFolderSource
         source = ImageFolderSource(data, H, device, data_name=data_name, add_noise=add_noise,
                                    brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
-                                   seed=seed, rank=rank, world=world, workers=workers)
+                                   seed=seed, rank=rank, world=world, workers=workers, resize=resize)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -427,12 +428,8 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                    save_dir=save_dir, rank=rank, world=world, sync_bn=sync_bn)
 
 
-def main(argv=None):
+def build_parser():
     import argparse
-    import json
-    import time
-
-    from .config import cfg
     ap = argparse.ArgumentParser(description="RL training of the ISP policy, data-parallel over the GPUs torchrun gives it")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the full schedule)")
     ap.add_argument("--warmup", type=int, default=2, help="untimed iterations before the throughput clock starts")
@@ -456,7 +453,18 @@ def main(argv=None):
     ap.add_argument("--data-workers", type=int, default=4, help="decoding threads per rank")
     ap.add_argument("--gpus", type=int, default=None, help="start this many ranks (one per GPU) under torch.distributed.run "
                     "as a child process; without it the process is one rank of whatever torchrun set up")
-    a = ap.parse_args(argv)
+    ap.add_argument("--resize", default="host", choices=("host", "device"),
+                    help="where dataset images are resampled to --size: host (numpy, in the decoding threads) or device "
+                         "(a HIP kernel; use it for photo-sized datasets, where the host resample cannot keep up)")
+    return ap
+
+
+def main(argv=None):
+    import json
+    import time
+
+    from .config import cfg
+    a = build_parser().parse_args(argv)
     if a.gpus and a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import sys
         # the parent never touches the GPU: it starts the ranks as a child and exits with their code
@@ -491,7 +499,7 @@ def main(argv=None):
         tr = build_trainer(cfg, rank, world, device, a.batch, a.size, lr=a.lr, epochs=a.epochs, save_dir=a.save_dir,
                            sync_bn=a.sync_bn, detector_ckpt=a.detector_ckpt, isp_ckpt=a.isp_ckpt, seed=a.seed, tune_cache=cache,
                            data=a.data, data_name=a.data_name, add_noise=a.add_noise, brightness_range=a.bri_range,
-                           noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers)
+                           noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers, resize=a.resize)
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

@@ -108,6 +108,9 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tune-cache", default=None, help="detector engine autotune cache (JSON)")
     ap.add_argument("--workers", type=int, default=4, help="decoding threads")
+    ap.add_argument("--resize", default="host", choices=("host", "device"),
+                    help="where images are resampled to --img-size: host (numpy, in the decoding threads) or device "
+                         "(a HIP kernel; use it for photo-sized datasets, where the host resample cannot keep up)")
     return ap
 
 
@@ -214,7 +217,7 @@ def main(argv=None):
     # ---- data and detector engines (one per batch size that occurs)
     src = ImageFolderSource(source, a.img_size, dev, data_name=a.data_name, add_noise=a.add_noise,
                             brightness_range=a.bri_range, noise_level=a.noise_level, use_linear=a.use_linear,
-                            seed=a.seed, workers=a.workers)
+                            seed=a.seed, workers=a.workers, resize=a.resize)
     n_files = len(src)
     engines = {}
     for b in {min(a.batch_size, n_files), n_files % a.batch_size or a.batch_size}:

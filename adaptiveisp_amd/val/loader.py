@@ -145,20 +145,25 @@ def read_labels(path):
     return lb
 
 
-def load_letterboxed(path, img_size):
-    """The decode / geometry / label part of one letterboxed sample (auto=False, scaleup=False), shared by LODImages and
-    the training source (adaptiveisp_amd/data.py): load_image, then letterbox's resize to the un-padded size (only on a
-    ceil overshoot of load_image) WITHOUT the padding. Returns
-        (im HWC BGR uint8 un-padded, (top, left) of it in the frame, (H, W) of the frame, labels [k,5] class + xywh
-         normalised to the frame, shapes = ((h0, w0), ((h/h0, w/w0), (dw, dh))))."""
-    im, (h0, w0), (h, w) = load_image(path, img_size, augment=False)
-    ratio, new_unpad, pad, (top, bottom, left, right) = letterbox_geometry(im.shape[:2], img_size, False, False, False, 32)
-    if (im.shape[1], im.shape[0]) != tuple(new_unpad):
-        im = resize_linear_u8(im, new_unpad)
-    H, W = im.shape[0] + top + bottom, im.shape[1] + left + right
+def letterboxed_geometry(h0, w0, img_size):
+    """The pixel-free part of load_letterboxed for a decoded image of (h0, w0): the sizes load_image and letterbox resample
+    to, the placement in the frame and `shapes`. Returns
+        ((h, w) after load_image, (h2, w2) un-padded after letterbox's resize (== (h, w) unless load_image's ceil
+         overshoots), (top, left), (H, W) of the frame, ratio, pad, shapes)."""
+    r = img_size / max(h0, w0)
+    h, w = (math.ceil(h0 * r), math.ceil(w0 * r)) if r != 1 else (h0, w0)
+    ratio, new_unpad, pad, (top, bottom, left, right) = letterbox_geometry((h, w), img_size, False, False, False, 32)
+    h2, w2 = new_unpad[1], new_unpad[0]
     shapes = (h0, w0), ((h / h0, w / w0), pad)
+    return (h, w), (h2, w2), (top, left), (h2 + top + bottom, w2 + left + right), ratio, pad, shapes
+
+
+def letterboxed_labels(path, size, frame, ratio, pad):
+    """The labels of image `path` (YOLO txt beside it) in the letterboxed frame: normalised xywh (native) -> pixels of the
+    frame -> normalised to it. `size` = (h, w) after load_image, `frame` = (H, W)."""
+    (h, w), (H, W) = size, frame
     lb = read_labels(_label_path(path)).copy()
-    if lb.size:                                   # normalised xywh (native) -> pixels in the letterboxed frame -> normalised
+    if lb.size:
         cx, cy = lb[:, 1] * (ratio[0] * w) + pad[0], lb[:, 2] * (ratio[1] * h) + pad[1]
         bw, bh = lb[:, 3] * (ratio[0] * w), lb[:, 4] * (ratio[1] * h)
         x1, y1, x2, y2 = cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2
@@ -166,7 +171,20 @@ def load_letterboxed(path, img_size):
         y1, y2 = np.clip(y1, 0, H - 1e-3), np.clip(y2, 0, H - 1e-3)
         lb[:, 1], lb[:, 2] = (x1 + x2) / 2 / W, (y1 + y2) / 2 / H
         lb[:, 3], lb[:, 4] = (x2 - x1) / W, (y2 - y1) / H
-    return np.ascontiguousarray(im), (top, left), (H, W), lb, shapes
+    return lb
+
+
+def load_letterboxed(path, img_size):
+    """The decode / geometry / label part of one letterboxed sample (auto=False, scaleup=False), shared by LODImages and
+    the training source (adaptiveisp_amd/data.py): load_image, then letterbox's resize to the un-padded size (only on a
+    ceil overshoot of load_image) WITHOUT the padding. Returns
+        (im HWC BGR uint8 un-padded, (top, left) of it in the frame, (H, W) of the frame, labels [k,5] class + xywh
+         normalised to the frame, shapes = ((h0, w0), ((h/h0, w/w0), (dw, dh))))."""
+    im, (h0, w0), _ = load_image(path, img_size, augment=False)
+    size, (h2, w2), place, frame, ratio, pad, shapes = letterboxed_geometry(h0, w0, img_size)
+    if (im.shape[1], im.shape[0]) != (w2, h2):
+        im = resize_linear_u8(im, (w2, h2))
+    return np.ascontiguousarray(im), place, frame, letterboxed_labels(path, size, frame, ratio, pad), shapes
 
 
 def list_images(source):

@@ -176,6 +176,44 @@ int adaisp_unprocess(const uint8_t* src, const adaisp_unprocess_desc* desc, floa
                      uint64_t seed, unsigned flags, void* stream);
 
 /*
+ * Replay-pool resampling on the device: the pixel work of `load_image` (dataloaders.py:735-750: longer side to S, area
+ * filter when shrinking, bilinear otherwise) and of `letterbox`'s resize to the un-padded size (augmentations.py:111-141),
+ * uint8 HWC BGR -> uint8 HWC BGR, every image with its own sizes, mode and byte offsets. Each mode reproduces the
+ * project's numpy restatement of OpenCV's uint8 kernels (adaptiveisp_amd/val/loader.py) bit for bit:
+ *   ADAISP_RESIZE_COPY      (W, H) == (w, h)
+ *   ADAISP_RESIZE_LINEAR    resize_linear_u8: 11-bit taps, int32 horizontal pass,
+ *                           (((b0 * (t >> 4)) >> 16) + ((b1 * (b >> 4)) >> 16) + 2) >> 2
+ *   ADAISP_RESIZE_AREA_INT  resize_area_u8, integer factors (fx = W / w, fy = H / h): integer block sum, then
+ *                           (sum + 2) >> 2 for 2 x 2 and rint(float(sum) * scale) otherwise, scale = float32(1 / (fx fy))
+ *   ADAISP_RESIZE_AREA      resize_area_u8, general factors: the fp32 weights of _area_weights, horizontal pass then
+ *                           vertical pass, each a sequence of one fp32 multiply then one fp32 add in source order;
+ *                           round half to even, clip
+ * The host builds the taps (adaptiveisp_amd/resize.py); they live in `tabs`, 32-bit words (floats by their bits):
+ *   LINEAR   at tab_x: i0[w], i1[w], w0[w], w1[w] (_linear_taps); at tab_y the same over h
+ *   AREA     at tab_x: ptr[w + 1], idx[nnz], weight[nnz] with nnz = ptr[w] (the nonzeros of row x of _area_weights, in
+ *            source order, CSR); at tab_y the same over h
+ * An image whose pixels or taps do not lie inside src_bytes / dst_bytes / tab_words, or whose mode is unknown, is not
+ * written; source indices read from the taps are clamped to the image. No allocation, no host synchronisation:
+ * capturable in a hipGraph. B <= 65535; max_h, max_w (the largest destination size of the batch: the grid) <= 32768.
+ */
+#define ADAISP_RESIZE_COPY 0
+#define ADAISP_RESIZE_LINEAR 1
+#define ADAISP_RESIZE_AREA_INT 2
+#define ADAISP_RESIZE_AREA 3
+typedef struct adaisp_resize_desc {
+    int64_t src_offset;        /* byte offset of the source image's first pixel in src                           */
+    int64_t dst_offset;        /* byte offset of the destination image in dst                                    */
+    int64_t tab_x, tab_y;      /* word offsets of the horizontal / vertical taps in tabs (LINEAR, AREA)          */
+    int32_t src_h, src_w;      /* source size                                                                    */
+    int32_t dst_h, dst_w;      /* destination size                                                               */
+    int32_t mode;              /* ADAISP_RESIZE_*                                                                */
+    float scale;               /* AREA_INT: float32(1 / (fx * fy))                                               */
+} adaisp_resize_desc;
+int adaisp_resize_u8(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t dst_bytes,
+                     const adaisp_resize_desc* desc, const int32_t* tabs, size_t tab_words, int B, int max_h, int max_w,
+                     void* stream);
+
+/*
  * Image export: planar fp32 RGB img [B,3,H,W] -> interleaved uint8 BGR out [B,H,W,3] (cv2.imwrite's channel order), in one
  * launch, with the arithmetic of the reference's `save_img` (util.py:21-40) and OpenCV's float -> 8U conversion:
  * NaN -> 0, clip to [0, 1], * 255.0f in fp32, round half to even. Any pointer alignment (16-byte loads where the

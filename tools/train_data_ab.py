@@ -4,10 +4,13 @@
 into a temporary directory, then runs `python -m adaptiveisp_amd.train` for the three arms in interleaved fresh child
 processes, each under its own time limit, and prints ms_per_iter per run and the median per arm (one JSON line each).
     python tools/train_data_ab.py [--rounds 3] [--iters 200] [--batch 8] [--size 512] [--images 64] [--workers 4]
-                                  [--photo-sizes]
+                                  [--photo-sizes] [--resize host|device|both]
 By default the images are S on the longer side, so the decode is PIL alone; --photo-sizes makes load_image's area
 resampler run on every image (the numpy restatement of cv2's INTER_AREA, val/loader.py: ~1 s per 640 x 480 image on one
-core), which the trainer then waits for. The tool also prints the host decode rate with `workers` threads."""
+core), which the trainer then waits for with `--resize host`. `--resize device` runs the dataset arms with the resample on
+the device (adaisp_resize_u8: the worker threads only decode); `both` runs the host and the device arms. The tool also
+prints the host decode rate with `workers` threads: the full host path (decode + resample + letterbox) and, for the
+device arms, the decode alone."""
 import argparse
 import json
 import os
@@ -57,6 +60,8 @@ def main():
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--photo-sizes", action="store_true", help="camera-sized images (load_image resamples every one)")
+    ap.add_argument("--resize", default="host", choices=("host", "device", "both"),
+                    help="where the dataset arms resample (both: one arm of each per dataset kind)")
     ap.add_argument("--timeout", type=int, default=600, help="seconds per child")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
@@ -65,16 +70,24 @@ def main():
         sys.path.insert(0, ROOT)
         import time
         from concurrent.futures import ThreadPoolExecutor
-        from adaptiveisp_amd.val.loader import list_images, load_letterboxed
+        from adaptiveisp_amd.val.loader import imread_bgr, list_images, load_letterboxed
         files = list_images(tmp)[:16]
-        with ThreadPoolExecutor(max(a.workers, 1)) as ex:
-            t0 = time.perf_counter()
-            list(ex.map(lambda f: load_letterboxed(f, a.size), files))
-            rate = len(files) / (time.perf_counter() - t0)
-        print(json.dumps({"decode_images_per_s": round(rate, 1), "workers": a.workers, "photo_sizes": a.photo_sizes}), flush=True)
+        rates = {}
+        for kind, fn in (("host_resize", lambda f: load_letterboxed(f, a.size)), ("decode_only", imread_bgr)):
+            if kind == "host_resize" and a.resize == "device":
+                continue
+            with ThreadPoolExecutor(max(a.workers, 1)) as ex:
+                t0 = time.perf_counter()
+                list(ex.map(fn, files))
+                rates[kind] = round(len(files) / (time.perf_counter() - t0), 1)
+        print(json.dumps({"decode_images_per_s": rates, "workers": a.workers, "photo_sizes": a.photo_sizes}), flush=True)
         common = ["--batch", str(a.batch), "--size", str(a.size), "--iters", str(a.iters + a.warmup), "--warmup", str(a.warmup)]
-        arms = {"synthetic": [], "lod": ["--data", tmp, "--data-name", "lod", "--data-workers", str(a.workers)],
-                "coco_noise": ["--data", tmp, "--data-name", "coco", "--add-noise", "--data-workers", str(a.workers)]}
+        arms = {"synthetic": []}
+        for resize in (("host", "device") if a.resize == "both" else (a.resize,)):
+            tag = "" if resize == "host" else "_device"
+            arms["lod" + tag] = ["--data", tmp, "--data-name", "lod", "--data-workers", str(a.workers), "--resize", resize]
+            arms["coco_noise" + tag] = ["--data", tmp, "--data-name", "coco", "--add-noise", "--data-workers",
+                                        str(a.workers), "--resize", resize]
         res = {k: [] for k in arms}
         for r in range(a.rounds):
             for name, extra in arms.items():
@@ -89,7 +102,8 @@ def main():
         base = statistics.median(res["synthetic"])
         print(json.dumps({"median_ms_per_iter": {k: statistics.median(v) for k, v in res.items()},
                           "vs_synthetic": {k: round(statistics.median(v) / base - 1, 4) for k, v in res.items()},
-                          "runs": res, "batch": a.batch, "size": a.size, "iters": a.iters, "workers": a.workers}), flush=True)
+                          "runs": res, "batch": a.batch, "size": a.size, "iters": a.iters, "workers": a.workers,
+                          "photo_sizes": a.photo_sizes, "resize": a.resize}), flush=True)
 
 
 if __name__ == "__main__":
