@@ -19,6 +19,37 @@ static void magic_div(unsigned d, unsigned* magic, int* sh) {
     *sh = L - 1;
 }
 
+// What a launcher's status means to the caller. hipErrorInvalidValue is the launchers' "this kernel does not serve the shape":
+// the entries that name ONE kernel report it as `on_invalid` = ADAYOLO_ESHAPE.
+static int code(hipError_t e, int on_invalid = ADAYOLO_ELAUNCH) {
+    if (e == hipErrorInvalidValue) return on_invalid;
+    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+}
+
+// The fields of a conv launch behind an entry's own checks: tensors, geometry and its limits (M < 2^31, input < 2^39 elements),
+// the two divisions. Everything else is zero / ConvArgs' default. ADAYOLO_OK or ADAYOLO_ESHAPE.
+static int conv_fill(ConvArgs& a, const void* in, int in_cstride, const void* weight, const float* bias, const void* residual,
+                     int res_cstride, void* out, int out_cstride, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
+                     int pad, int act) {
+    a = ConvArgs{};
+    a.in = static_cast<const unsigned short*>(in); a.in_cs = in_cstride;
+    a.w = static_cast<const unsigned short*>(weight); a.bias = bias;
+    a.res = static_cast<const unsigned short*>(residual); a.res_cs = res_cstride;
+    a.out = static_cast<unsigned short*>(out); a.out_cs = out_cstride;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+    a.ks = ksize; a.stride = stride; a.pad = pad; a.act = act;
+    a.Ho = (H + 2 * pad - ksize) / stride + 1;
+    a.Wo = (W + 2 * pad - ksize) / stride + 1;
+    const long M = (long)B * a.Ho * a.Wo;
+    if (M > 0x7fffffffL || (long)B * H * W * in_cstride > 0x7fffffffffL) return ADAYOLO_ESHAPE;
+    a.M = (int)M;
+    magic_div((unsigned)(a.Ho * a.Wo), &a.magic_hw, &a.sh_hw);
+    magic_div((unsigned)a.Wo, &a.magic_w, &a.sh_w);
+    return ADAYOLO_OK;
+}
+
+static bool bad_act(int act) { return act != ADAYOLO_ACT_NONE && act != ADAYOLO_ACT_SILU; }
+
 // Shared checks + derived fields of a conv launch (every conv entry point below). ADAYOLO_OK or the error to return.
 static int conv_args(ConvArgs& a, const void* in, int in_cstride, const void* weight, const float* bias, const void* residual,
                      int res_cstride, void* out, int out_cstride, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
@@ -29,23 +60,56 @@ static int conv_args(ConvArgs& a, const void* in, int in_cstride, const void* we
     if (Cin % 8 || Cout % 8 || in_cstride % 8 || out_cstride % 8 || in_cstride < Cin || out_cstride < Cout)
         return ADAYOLO_ESHAPE;
     if (residual && (res_cstride % 8 || res_cstride < Cout)) return ADAYOLO_ESHAPE;
-    if (act != ADAYOLO_ACT_NONE && act != ADAYOLO_ACT_SILU) return ADAYOLO_EINVAL;
-    a.in = static_cast<const unsigned short*>(in); a.in_cs = in_cstride;
-    a.w = static_cast<const unsigned short*>(weight); a.bias = bias;
-    a.res = static_cast<const unsigned short*>(residual); a.res_cs = res_cstride;
-    a.out = static_cast<unsigned short*>(out); a.out_cs = out_cstride;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.ks = ksize; a.stride = stride; a.pad = ksize / 2; a.act = act;
-    a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
-    a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
-    const long M = (long)B * a.Ho * a.Wo;
-    if (M > 0x7fffffffL || (long)B * H * W * in_cstride > 0x7fffffffffL) return ADAYOLO_ESHAPE;
-    a.M = (int)M; a.mtiles = a.ntiles = 0;
-    a.w2 = nullptr; a.bias2 = nullptr; a.out2 = nullptr; a.out2_cs = 0;
-    a.pre = nullptr; a.pre_cs = 0;
-    magic_div((unsigned)(a.Ho * a.Wo), &a.magic_hw, &a.sh_hw);
-    magic_div((unsigned)a.Wo, &a.magic_w, &a.sh_w);
-    return ADAYOLO_OK;
+    if (bad_act(act)) return ADAYOLO_EINVAL;
+    return conv_fill(a, in, in_cstride, weight, bias, residual, res_cstride, out, out_cstride, B, H, W, Cin, Cout, ksize, stride,
+                     ksize / 2, act);
+}
+
+// ---- which kernel family a variant number names (include/adayolo.h); every entry accepts its own set of families
+enum Family { kNoFamily, kDma, kDma2, kSmall, kPp, kPp128, kPq, kWs, kSplitK };
+constexpr unsigned fam(Family f) { return 1u << f; }
+static Family family_of(int variant) {
+    switch (variant) {
+        case 2: return kDma;
+        case 5: case 22: case 26: case 27: return kDma2;
+        case 40: return kSmall;                          // 3x3, Cin 32 / 64 only
+        case 50: return kPp;                             // Cin % 64 == 0, Cout % 256 == 0 only
+        case 60: return kPp128;                          // Cin % 64 == 0, Cout % 128 == 0 only
+        case 80: case 85: return kPq;                    // Cin % 32 == 0, Cout % 128 == 0 (85: 128-pixel tile)
+        case 90: return kWs;                             // 3x3 s1, Cin 32 / 64, Cout % 64 == 0, SiLU
+        default: return variant >= ADAYOLO_SPLITK_BASE + 2 && variant <= ADAYOLO_SPLITK_BASE + 16 ? kSplitK : kNoFamily;
+    }
+}
+static hipError_t launch_family(Family f, const ConvArgs& a, hipStream_t s, int variant) {
+    switch (f) {
+        case kDma: return launch_conv_dma(a, s, variant);
+        case kDma2: return launch_conv_dma2(a, s, variant);
+        case kSmall: return launch_conv_small(a, s, variant);
+        case kPp: return launch_conv_pp(a, s, variant);
+        case kPp128: return launch_conv_pp128(a, s, variant);
+        case kPq: return launch_conv_pq(a, s, variant);
+        case kWs: return launch_conv_ws(a, s, variant);
+        default: return hipErrorInvalidValue;
+    }
+}
+// The entries that name one kernel: a variant outside `accept` is ADAYOLO_EINVAL; a split-K variant needs a split that serves the
+// shape (ADAYOLO_ESHAPE) and its workspace (ADAYOLO_EINVAL), in this order
+static int conv_launch(unsigned accept, const ConvArgs& a, int variant, void* stream, void* workspace = nullptr,
+                       size_t workspace_bytes = 0, int on_invalid = ADAYOLO_ESHAPE) {
+    const Family f = family_of(variant);
+    if (!(accept & fam(f))) return ADAYOLO_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (f != kSplitK) return code(launch_family(f, a, s, variant), on_invalid);
+    const int S = variant - ADAYOLO_SPLITK_BASE;
+    const size_t need = conv_pp128_splitk_bytes(a, S);
+    if (need == 0) return ADAYOLO_ESHAPE;
+    if (!workspace || workspace_bytes < need) return ADAYOLO_EINVAL;
+    return code(launch_conv_pp128_splitk(a, s, S, workspace, workspace_bytes), on_invalid);
+}
+
+// a frame of H image rows at pad_top inside Hp letterboxed rows
+static bool bad_frame(int B, int H, int W, int Hp, int pad_top) {
+    return B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp;
 }
 
 extern "C" {
@@ -73,31 +137,15 @@ int adayolo_conv_fwd_variant(const void* in, int in_cstride, const void* weight,
     if (rc != ADAYOLO_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (variant == 0) variant = ADAYOLO_DEFAULT_VARIANT;
-    hipError_t e = hipErrorInvalidValue;
-    bool known = false;
-    switch (variant) {
-        case 2: known = true; e = launch_conv_dma(a, s, variant); break;
-        case 5: case 22: case 26: case 27: known = true; e = launch_conv_dma2(a, s, variant); break;
-        case 40: known = true; e = launch_conv_small(a, s, variant); break;       // 3x3, Cin 32 / 64 only
-        case 50: known = true; e = launch_conv_pp(a, s, variant); break;          // Cin % 64 == 0, Cout % 256 == 0 only
-        case 60: known = true; e = launch_conv_pp128(a, s, variant); break;       // Cin % 64 == 0, Cout % 128 == 0 only
-        case 80: case 85: known = true; e = launch_conv_pq(a, s, variant); break; // Cin % 32 == 0, Cout % 128 == 0 (85: 128-pixel tile)
-        case 90: known = true; e = launch_conv_ws(a, s, variant); break;          // 3x3 s1, Cin 32 / 64, Cout % 64 == 0, SiLU
-        default: break;
-    }
+    Family f = family_of(variant);
+    if (f == kSplitK) f = kNoFamily;                                              // (adayolo_conv_splitk_fwd's)
 #ifdef ADAYOLO_MEASURE
-    if (!known) {
-        known = true;
-        if (variant >= 90) e = launch_conv_ws(a, s, variant);
-        else if (variant >= 80) e = launch_conv_pq(a, s, variant);
-        else if (variant >= 60) e = launch_conv_pp128(a, s, variant);
-        else if (variant >= 50) e = launch_conv_pp(a, s, variant);
-        else e = launch_conv_dma2(a, s, variant);
-    }
+    if (f == kNoFamily) f = variant >= 90 ? kWs : variant >= 80 ? kPq : variant >= 60 ? kPp128 : variant >= 50 ? kPp : kDma2;
 #endif
-    if (!known) return ADAYOLO_EINVAL;                                            // not a kernel of this library
+    if (f == kNoFamily) return ADAYOLO_EINVAL;                                    // not a kernel of this library
+    hipError_t e = launch_family(f, a, s, variant);
     if (e == hipErrorInvalidValue && variant >= 40) e = launch_conv_dma(a, s, ADAYOLO_DEFAULT_VARIANT);   // shape not served
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(e);
 }
 
 int adayolo_conv_fused1x1_fwd(const void* in, int in_cstride, const void* weight, const float* bias, const void* residual,
@@ -113,25 +161,14 @@ int adayolo_conv_fused1x1_fwd(const void* in, int in_cstride, const void* weight
         in_cstride < Cin || out_cstride < Cout || out2_cstride < Cout2)
         return ADAYOLO_ESHAPE;
     if (residual && (res_cstride % 8 || res_cstride < Cout)) return ADAYOLO_ESHAPE;
-    if (act != ADAYOLO_ACT_NONE && act != ADAYOLO_ACT_SILU) return ADAYOLO_EINVAL;
+    if (bad_act(act)) return ADAYOLO_EINVAL;
     ConvArgs a;
-    a.in = static_cast<const unsigned short*>(in); a.in_cs = in_cstride;
-    a.w = static_cast<const unsigned short*>(weight); a.bias = bias;
-    a.res = static_cast<const unsigned short*>(residual); a.res_cs = res_cstride;
-    a.out = static_cast<unsigned short*>(out); a.out_cs = out_cstride;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.ks = ksize; a.stride = stride; a.pad = ksize / 2; a.act = act;
-    a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
-    a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
-    const long M = (long)B * a.Ho * a.Wo;
-    if (M > 0x7fffffffL || (long)B * H * W * in_cstride > 0x7fffffffffL) return ADAYOLO_ESHAPE;
-    a.M = (int)M; a.mtiles = a.ntiles = 0;
-    magic_div((unsigned)(a.Ho * a.Wo), &a.magic_hw, &a.sh_hw);
-    magic_div((unsigned)a.Wo, &a.magic_w, &a.sh_w);
+    const int rc = conv_fill(a, in, in_cstride, weight, bias, residual, res_cstride, out, out_cstride, B, H, W, Cin, Cout, ksize,
+                             stride, ksize / 2, act);
+    if (rc != ADAYOLO_OK) return rc;
     a.w2 = static_cast<const unsigned short*>(weight2); a.bias2 = bias2;
     a.out2 = static_cast<unsigned short*>(out2); a.out2_cs = out2_cstride;
-    a.pre = nullptr; a.pre_cs = 0;
-    return launch_conv_pp(a, static_cast<hipStream_t>(stream), 50) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_conv_pp(a, static_cast<hipStream_t>(stream), 50));
 }
 
 int adayolo_conv1x1_stream_fwd(const void* in, int in_cstride, const void* weight_fragments, const float* bias, void* out,
@@ -140,9 +177,7 @@ int adayolo_conv1x1_stream_fwd(const void* in, int in_cstride, const void* weigh
     const int rc = conv_args(a, in, in_cstride, weight_fragments, bias, nullptr, 0, out, out_cstride, B, H, W, Cin, Cout, 1, 1, act);
     if (rc != ADAYOLO_OK) return rc;
     if (in == out) return ADAYOLO_EINVAL;
-    const hipError_t e = launch_conv_k1(a, static_cast<hipStream_t>(stream));
-    if (e == hipErrorInvalidValue) return ADAYOLO_ESHAPE;                 // Cin not in {256, 512} or Cout % 256 != 0
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_conv_k1(a, static_cast<hipStream_t>(stream)), ADAYOLO_ESHAPE);   // Cin not in {256, 512} or Cout % 256 != 0
 }
 
 // ---- persistent chain: host-side tables ------------------------------------------------------------------------------------
@@ -288,6 +323,14 @@ int chain_plan(const adayolo_chain_layer* L, int n, ChainPlan& P, bool tables) {
     return ADAYOLO_OK;
 }
 
+// the workspace image: zero counters, then the three tables
+void chain_image(const ChainPlan& P, unsigned char* img) {
+    memset(img, 0, P.bytes);
+    memcpy(img + P.off_layers, P.layers.data(), P.layers.size() * sizeof(ConvArgs));
+    memcpy(img + P.off_heads, P.heads.data(), P.heads.size() * sizeof(ChainHead));
+    memcpy(img + P.off_deps, P.deps.data(), P.deps.size() * sizeof(ChainDeps));
+}
+
 int device_cus() {
     static int cus = 0;
     if (!cus) {
@@ -310,11 +353,7 @@ int adayolo_conv_chain_tables(const adayolo_chain_layer* layers, int n, void* ho
     const int rc = chain_plan(layers, n, P, true);
     if (rc != ADAYOLO_OK) return rc;
     if (!host_image || bytes < P.bytes) return ADAYOLO_EINVAL;
-    unsigned char* img = static_cast<unsigned char*>(host_image);
-    memset(img, 0, P.bytes);
-    memcpy(img + P.off_layers, P.layers.data(), P.layers.size() * sizeof(ConvArgs));
-    memcpy(img + P.off_heads, P.heads.data(), P.heads.size() * sizeof(ChainHead));
-    memcpy(img + P.off_deps, P.deps.data(), P.deps.size() * sizeof(ChainDeps));
+    chain_image(P, static_cast<unsigned char*>(host_image));
     if (info) {
         info[0] = (int32_t)P.heads.size(); info[1] = P.ndone; info[2] = (int32_t)P.off_layers; info[3] = (int32_t)P.off_heads;
         info[4] = (int32_t)P.off_deps; info[5] = (int32_t)sizeof(ConvArgs);
@@ -358,10 +397,8 @@ int adayolo_conv_chain_prepare(const adayolo_chain_layer* layers, int n, void* w
     const int rc = chain_plan(layers, n, P, true);
     if (rc != ADAYOLO_OK) return rc;
     if (!workspace || workspace_bytes < P.bytes || ((uintptr_t)workspace & 63)) return ADAYOLO_EINVAL;
-    std::vector<unsigned char> img(P.bytes, 0);
-    memcpy(img.data() + P.off_layers, P.layers.data(), P.layers.size() * sizeof(ConvArgs));
-    memcpy(img.data() + P.off_heads, P.heads.data(), P.heads.size() * sizeof(ChainHead));
-    memcpy(img.data() + P.off_deps, P.deps.data(), P.deps.size() * sizeof(ChainDeps));
+    std::vector<unsigned char> img(P.bytes);
+    chain_image(P, img.data());
     if (hipMemcpy(workspace, img.data(), P.bytes, hipMemcpyHostToDevice) != hipSuccess) return ADAYOLO_ELAUNCH;
     std::lock_guard<std::mutex> lock(g_chain_mu);
     if (!g_chain_flags) {
@@ -399,7 +436,7 @@ int adayolo_conv_chain_fwd(const adayolo_chain_layer* layers, int n, void* works
     static const int grid_cap = [] { const char* e = getenv("ADAYOLO_CHAIN_GRID"); return e ? atoi(e) : 0; }();
     c.stagger = stagger;
     const int grid = grid_cap > 0 && grid_cap < device_cus() ? grid_cap : device_cus();
-    return launch_conv_chain(c, grid, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_conv_chain(c, grid, static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_conv_chain_status(const void* workspace) {
@@ -425,8 +462,8 @@ int adayolo_bottleneck256_fwd(const void* x, int x_cstride, const void* weight1,
     if ((long)B * H * W * (x_cstride > out_cstride ? x_cstride : out_cstride) > 0x7fffffffffL ||
         (long)B * ((H + 15) / 16) * ((W + 15) / 16) > 0x7fffffffL)
         return ADAYOLO_ESHAPE;
-    return launch_bottleneck256(x, x_cstride, weight1, bias1, weight2, bias2, out, out_cstride, B, H, W,
-                                static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_bottleneck256(x, x_cstride, weight1, bias1, weight2, bias2, out, out_cstride, B, H, W,
+                                     static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_bottleneck_ws_fwd(const void* x, int x_cstride, const void* weight1, const float* bias1, const void* weight2,
@@ -434,10 +471,8 @@ int adayolo_bottleneck_ws_fwd(const void* x, int x_cstride, const void* weight1,
     if (!x || !weight1 || !bias1 || !weight2 || !bias2 || !out || x == out) return ADAYOLO_EINVAL;
     if (B <= 0 || H <= 0 || W <= 0) return ADAYOLO_EINVAL;
     if ((C != 64 && C != 128) || x_cstride % 8 || out_cstride % 8 || x_cstride < C || out_cstride < C) return ADAYOLO_ESHAPE;
-    const hipError_t e = launch_bottleneck_ws(x, x_cstride, weight1, bias1, weight2, bias2, out, out_cstride, B, H, W, C,
-                                              static_cast<hipStream_t>(stream));
-    if (e == hipErrorInvalidValue) return ADAYOLO_ESHAPE;                  // a tensor beyond 32-bit byte offsets
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_bottleneck_ws(x, x_cstride, weight1, bias1, weight2, bias2, out, out_cstride, B, H, W, C,
+                                     static_cast<hipStream_t>(stream)), ADAYOLO_ESHAPE);      // a tensor beyond 32-bit byte offsets
 }
 
 int adayolo_conv_keep_fwd(const void* in, int in_cstride, const void* weight, const float* bias, const void* residual,
@@ -449,21 +484,16 @@ int adayolo_conv_keep_fwd(const void* in, int in_cstride, const void* weight, co
                              ksize, stride, act);
     if (rc != ADAYOLO_OK) return rc;
     if (pre_cstride % 8 || pre_cstride < Cout) return ADAYOLO_ESHAPE;
-    const bool dma2 = variant == 5 || variant == 22 || variant == 26 || variant == 27;
-    const bool pq = variant == 80 || variant == 85;
-    if (!dma2 && !pq && variant != 60) return ADAYOLO_EINVAL;       // the kernels whose epilogue has the second output
     a.pre = static_cast<unsigned short*>(pre); a.pre_cs = pre_cstride;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = dma2 ? launch_conv_dma2(a, s, variant) : pq ? launch_conv_pq(a, s, variant) : launch_conv_pp128(a, s, variant);
-    if (e == hipErrorInvalidValue) return ADAYOLO_ESHAPE;    // this kernel does not serve the shape: the caller keeps two launches
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    // the kernels whose epilogue has the second output; ADAYOLO_ESHAPE: this one does not serve the shape, the caller keeps two launches
+    return conv_launch(fam(kDma2) | fam(kPq) | fam(kPp128), a, variant, stream);
 }
 
 size_t adayolo_conv_splitk_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int variant) {
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || ksize < 1 || ksize > 3 || (stride != 1 && stride != 2))
         return 0;
-    if (variant < ADAYOLO_SPLITK_BASE + 2 || variant > ADAYOLO_SPLITK_BASE + 16) return 0;
-    ConvArgs a;
+    if (family_of(variant) != kSplitK) return 0;
+    ConvArgs a{};
     a.Cin = Cin; a.Cout = Cout; a.ks = ksize;
     const int pad = ksize / 2;
     // ksize 2 = the stride-2 data gradient's form (adayolo_conv_s2grad_fwd: H x W is its Ho x Wo grid, Cout = 4 x channels)
@@ -479,19 +509,14 @@ int adayolo_conv_splitk_fwd(const void* in, int in_cstride, const void* weight, 
                             int Cin, int Cout, int ksize, int stride, int act, int variant, void* workspace,
                             size_t workspace_bytes, void* stream) {
     if (!workspace) return ADAYOLO_EINVAL;
-    if (variant < ADAYOLO_SPLITK_BASE + 2 || variant > ADAYOLO_SPLITK_BASE + 16) return ADAYOLO_EINVAL;
+    if (family_of(variant) != kSplitK) return ADAYOLO_EINVAL;
     ConvArgs a;
     const int rc = conv_args(a, in, in_cstride, weight, bias, residual, res_cstride, out, out_cstride, B, H, W, Cin, Cout,
                              ksize, stride, act);
     if (rc != ADAYOLO_OK) return rc;
     if (pre && (pre_cstride % 8 || pre_cstride < Cout)) return ADAYOLO_ESHAPE;
     a.pre = static_cast<unsigned short*>(pre); a.pre_cs = pre ? pre_cstride : 0;
-    const size_t need = conv_pp128_splitk_bytes(a, variant - ADAYOLO_SPLITK_BASE);
-    if (need == 0) return ADAYOLO_ESHAPE;                    // this split does not serve the shape
-    if (workspace_bytes < need) return ADAYOLO_EINVAL;
-    const hipError_t e = launch_conv_pp128_splitk(a, static_cast<hipStream_t>(stream), variant - ADAYOLO_SPLITK_BASE, workspace,
-                                                  workspace_bytes);
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return conv_launch(fam(kSplitK), a, variant, stream, workspace, workspace_bytes, ADAYOLO_ELAUNCH);
 }
 
 int adayolo_conv_dsilu_fwd(const void* in, int in_cstride, const void* weight, const float* bias, const void* residual,
@@ -507,24 +532,8 @@ int adayolo_conv_dsilu_fwd(const void* in, int in_cstride, const void* weight, c
     a.out = static_cast<unsigned short*>(out); a.out_cs = out ? out_cstride : 0;
     a.pre = static_cast<unsigned short*>(const_cast<void*>(pre)); a.pre_cs = pre_cstride;      // an input here
     a.gpre = static_cast<unsigned short*>(grad_pre); a.gpre_cs = gp_cstride;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e;
-    if (variant >= ADAYOLO_SPLITK_BASE + 2 && variant <= ADAYOLO_SPLITK_BASE + 16) {
-        const size_t need = conv_pp128_splitk_bytes(a, variant - ADAYOLO_SPLITK_BASE);
-        if (need == 0) return ADAYOLO_ESHAPE;
-        if (!workspace || workspace_bytes < need) return ADAYOLO_EINVAL;
-        e = launch_conv_pp128_splitk(a, s, variant - ADAYOLO_SPLITK_BASE, workspace, workspace_bytes);
-    } else if (variant == 5 || variant == 22 || variant == 26 || variant == 27) {
-        e = launch_conv_dma2(a, s, variant);
-    } else if (variant == 60) {
-        e = launch_conv_pp128(a, s, variant);
-    } else if (variant == 80 || variant == 85) {
-        e = launch_conv_pq(a, s, variant);
-    } else {
-        return ADAYOLO_EINVAL;                               // the kernels whose epilogue has this form
-    }
-    if (e == hipErrorInvalidValue) return ADAYOLO_ESHAPE;    // the named kernel does not serve the shape
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    // the kernels whose epilogue has this form; ADAYOLO_ESHAPE: the named one does not serve the shape
+    return conv_launch(fam(kSplitK) | fam(kDma2) | fam(kPp128) | fam(kPq), a, variant, stream, workspace, workspace_bytes);
 }
 
 int adayolo_conv_s2grad_fwd(const void* grad_out, int go_cstride, const void* weight4, const float* bias4, const void* residual,
@@ -539,36 +548,20 @@ int adayolo_conv_s2grad_fwd(const void* grad_out, int go_cstride, const void* we
     if (pre && (pre_cstride % 8 || pre_cstride < Cin || gp_cstride % 8 || gp_cstride < Cin)) return ADAYOLO_ESHAPE;
     const long M = (long)B * Ho * Wo;
     if (4 * M > 0x7fffffffL || 4 * M * (gi_cstride > gp_cstride ? gi_cstride : gp_cstride) > 0x7fffffffffL) return ADAYOLO_ESHAPE;
-    ConvArgs a;                                               // a 2x2 stride-1 conv over the Ho x Wo grid, zero beyond its far edges
+    ConvArgs a{};                                             // a 2x2 stride-1 conv over the Ho x Wo grid, zero beyond its far edges
     a.in = static_cast<const unsigned short*>(grad_out); a.in_cs = go_cstride;
     a.w = static_cast<const unsigned short*>(weight4); a.bias = bias4;
     a.res = static_cast<const unsigned short*>(residual); a.res_cs = residual ? res_cstride : 0;
     a.out = static_cast<unsigned short*>(grad_in); a.out_cs = grad_in ? gi_cstride : 0;
     a.B = B; a.H = Ho; a.W = Wo; a.Cin = Cout; a.Cout = 4 * Cin;
     a.ks = 2; a.stride = 1; a.pad = 0; a.act = ADAYOLO_ACT_NONE;
-    a.Ho = Ho; a.Wo = Wo; a.M = (int)M; a.mtiles = a.ntiles = 0;
-    a.w2 = nullptr; a.bias2 = nullptr; a.out2 = nullptr; a.out2_cs = 0;
+    a.Ho = Ho; a.Wo = Wo; a.M = (int)M;
     a.pre = static_cast<unsigned short*>(const_cast<void*>(pre)); a.pre_cs = pre ? pre_cstride : 0;
     a.gpre = static_cast<unsigned short*>(grad_pre); a.gpre_cs = grad_pre ? gp_cstride : 0;
     a.d2s_c = Cin;
     magic_div((unsigned)(Ho * Wo), &a.magic_hw, &a.sh_hw);
     magic_div((unsigned)Wo, &a.magic_w, &a.sh_w);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e;
-    if (variant >= ADAYOLO_SPLITK_BASE + 2 && variant <= ADAYOLO_SPLITK_BASE + 16) {
-        const size_t need = conv_pp128_splitk_bytes(a, variant - ADAYOLO_SPLITK_BASE);
-        if (need == 0) return ADAYOLO_ESHAPE;
-        if (!workspace || workspace_bytes < need) return ADAYOLO_EINVAL;
-        e = launch_conv_pp128_splitk(a, s, variant - ADAYOLO_SPLITK_BASE, workspace, workspace_bytes);
-    } else if (variant == 5 || variant == 22 || variant == 26 || variant == 27) {
-        e = launch_conv_dma2(a, s, variant);
-    } else if (variant == 60) {
-        e = launch_conv_pp128(a, s, variant);
-    } else {
-        return ADAYOLO_EINVAL;
-    }
-    if (e == hipErrorInvalidValue) return ADAYOLO_ESHAPE;
-    return e == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return conv_launch(fam(kSplitK) | fam(kDma2) | fam(kPp128), a, variant, stream, workspace, workspace_bytes);
 }
 
 int adayolo_conv_fwd(const void* in, int in_cstride, const void* weight, const float* bias, const void* residual,
@@ -578,41 +571,40 @@ int adayolo_conv_fwd(const void* in, int in_cstride, const void* weight, const f
                                     Cin, Cout, ksize, stride, act, 0, stream);
 }
 
+// the three stem entries: `pre` (with want_pre) is the kept pre-activation
+static int stem(const float* img, const float* weight, const float* bias, void* out, int out_cstride, bool want_pre, void* pre,
+                int pre_cstride, int B, int H, int W, int Hp, int pad_top, float pad_value, int Cout, int act, void* stream) {
+    if (!img || !weight || !bias || !out || (want_pre && !pre)) return ADAYOLO_EINVAL;
+    if (bad_frame(B, H, W, Hp, pad_top)) return ADAYOLO_EINVAL;
+    if (bad_act(act)) return ADAYOLO_EINVAL;
+    if (Cout != 32 || out_cstride % 8 || out_cstride < Cout || (want_pre && (pre_cstride % 8 || pre_cstride < Cout)) || B > 65535)
+        return ADAYOLO_ESHAPE;
+    return code(launch_stem(img, weight, bias, out, out_cstride, B, H, W, Hp, pad_top, pad_value, act,
+                            static_cast<hipStream_t>(stream), pre, pre_cstride));
+}
+
 int adayolo_stem_fwd(const float* img, const float* weight, const float* bias, void* out, int out_cstride, int B,
                      int H, int W, int Hp, int pad_top, float pad_value, int Cout, void* stream) {
-    if (!img || !weight || !bias || !out) return ADAYOLO_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp) return ADAYOLO_EINVAL;
-    if (Cout != 32 || out_cstride % 8 || out_cstride < Cout || B > 65535) return ADAYOLO_ESHAPE;
-    return launch_stem(img, weight, bias, out, out_cstride, B, H, W, Hp, pad_top, pad_value, ADAYOLO_ACT_SILU,
-                       static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return stem(img, weight, bias, out, out_cstride, false, nullptr, 0, B, H, W, Hp, pad_top, pad_value, Cout, ADAYOLO_ACT_SILU, stream);
 }
 
 int adayolo_stem_fwd_act(const float* img, const float* weight, const float* bias, void* out, int out_cstride, int B,
                          int H, int W, int Hp, int pad_top, float pad_value, int Cout, int act, void* stream) {
-    if (!img || !weight || !bias || !out) return ADAYOLO_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp) return ADAYOLO_EINVAL;
-    if (act != ADAYOLO_ACT_NONE && act != ADAYOLO_ACT_SILU) return ADAYOLO_EINVAL;
-    if (Cout != 32 || out_cstride % 8 || out_cstride < Cout || B > 65535) return ADAYOLO_ESHAPE;
-    return launch_stem(img, weight, bias, out, out_cstride, B, H, W, Hp, pad_top, pad_value, act,
-                       static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return stem(img, weight, bias, out, out_cstride, false, nullptr, 0, B, H, W, Hp, pad_top, pad_value, Cout, act, stream);
 }
 
 int adayolo_stem_keep_fwd(const float* img, const float* weight, const float* bias, void* out, int out_cstride, void* pre,
                           int pre_cstride, int B, int H, int W, int Hp, int pad_top, float pad_value, int Cout, void* stream) {
-    if (!img || !weight || !bias || !out || !pre) return ADAYOLO_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp) return ADAYOLO_EINVAL;
-    if (Cout != 32 || out_cstride % 8 || out_cstride < Cout || pre_cstride % 8 || pre_cstride < Cout || B > 65535) return ADAYOLO_ESHAPE;
-    return launch_stem(img, weight, bias, out, out_cstride, B, H, W, Hp, pad_top, pad_value, ADAYOLO_ACT_SILU,
-                       static_cast<hipStream_t>(stream), pre, pre_cstride) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return stem(img, weight, bias, out, out_cstride, true, pre, pre_cstride, B, H, W, Hp, pad_top, pad_value, Cout, ADAYOLO_ACT_SILU, stream);
 }
 
 int adayolo_letterbox_pack(const float* img, void* out, int out_cstride, int B, int H, int W, int Hp, int pad_top,
                            float pad_value, void* stream) {
     if (!img || !out) return ADAYOLO_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp) return ADAYOLO_EINVAL;
+    if (bad_frame(B, H, W, Hp, pad_top)) return ADAYOLO_EINVAL;
     if (out_cstride % 8 || out_cstride < 8 || B > 65535 || Hp > 65535) return ADAYOLO_ESHAPE;
-    return launch_letterbox_pack(img, out, out_cstride, B, H, W, Hp, pad_top, pad_value,
-                                 static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_letterbox_pack(img, out, out_cstride, B, H, W, Hp, pad_top, pad_value,
+                                      static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_stem_down_fwd(const float* img, const float* w_stem, const float* b_stem, const void* w_down,
@@ -622,10 +614,10 @@ int adayolo_stem_down_fwd(const float* img, const float* w_stem, const float* b_
     if (!img || !w_stem || !b_stem || !w_down || !b_down || !out) return ADAYOLO_EINVAL;
     if (w_next && (!b_next || !out_next)) return ADAYOLO_EINVAL;
     if (w_next && (out_next_cstride % 8 || out_next_cstride < 32)) return ADAYOLO_ESHAPE;
-    if (B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp) return ADAYOLO_EINVAL;
+    if (bad_frame(B, H, W, Hp, pad_top)) return ADAYOLO_EINVAL;
     if ((Hp & 1) || (W & 1) || out_cstride % 8 || out_cstride < 64 || B > 65535) return ADAYOLO_ESHAPE;
-    return launch_stem_down(img, w_stem, b_stem, w_down, b_down, out, out_cstride, B, H, W, Hp, pad_top, pad_value,
-                            w_next, b_next, out_next, out_next_cstride, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_stem_down(img, w_stem, b_stem, w_down, b_down, out, out_cstride, B, H, W, Hp, pad_top, pad_value,
+                                 w_next, b_next, out_next, out_next_cstride, static_cast<hipStream_t>(stream)));
 }
 
 static bool ok8(int C, int cs) { return C > 0 && C % 8 == 0 && cs % 8 == 0 && cs >= C; }
@@ -634,8 +626,8 @@ int adayolo_silu_fwd(const void* pre, int pre_cstride, const void* residual, int
                      int out_cstride, long npix, int C, void* stream) {
     if (!pre || !out || npix <= 0) return ADAYOLO_EINVAL;
     if (!ok8(C, pre_cstride) || !ok8(C, out_cstride) || (residual && !ok8(C, res_cstride))) return ADAYOLO_ESHAPE;
-    return launch_silu_fwd(pre, pre_cstride, residual, res_cstride, out, out_cstride, npix, C,
-                           static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_silu_fwd(pre, pre_cstride, residual, res_cstride, out, out_cstride, npix, C,
+                                static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_silu_bwd(const void* grad_out, int go_cstride, const void* pre, int pre_cstride, void* grad_pre,
@@ -643,40 +635,37 @@ int adayolo_silu_bwd(const void* grad_out, int go_cstride, const void* pre, int 
     if (!grad_out || npix <= 0 || (!grad_pre && !grad_res) || (grad_pre && !pre)) return ADAYOLO_EINVAL;
     if (!ok8(C, go_cstride) || (grad_pre && (!ok8(C, pre_cstride) || !ok8(C, gp_cstride))) ||
         (grad_res && !ok8(C, gr_cstride))) return ADAYOLO_ESHAPE;
-    return launch_silu_bwd(grad_out, go_cstride, pre, pre_cstride, grad_pre, gp_cstride, grad_res, gr_cstride,
-                           accumulate_res, npix, C, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_silu_bwd(grad_out, go_cstride, pre, pre_cstride, grad_pre, gp_cstride, grad_res, gr_cstride,
+                                accumulate_res, npix, C, static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_zero_insert2x(const void* in, int in_cstride, void* out, int out_cstride, int B, int Ho, int Wo, int H, int W,
                           int C, void* stream) {
     if (!in || !out || B <= 0 || Ho <= 0 || Wo <= 0 || H <= 0 || W <= 0) return ADAYOLO_EINVAL;
     if (!ok8(C, in_cstride) || !ok8(C, out_cstride) || (H + 1) / 2 != Ho || (W + 1) / 2 != Wo) return ADAYOLO_ESHAPE;
-    return launch_zero_insert(in, in_cstride, out, out_cstride, B, Ho, Wo, H, W, C, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_zero_insert(in, in_cstride, out, out_cstride, B, Ho, Wo, H, W, C, static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_upsample2x_bwd(const void* grad_out, int go_cstride, void* grad_in, int gi_cstride, int accumulate, int B,
                            int H, int W, int C, void* stream) {
     if (!grad_out || !grad_in || B <= 0 || H <= 0 || W <= 0) return ADAYOLO_EINVAL;
     if (!ok8(C, go_cstride) || !ok8(C, gi_cstride)) return ADAYOLO_ESHAPE;
-    return launch_upsample_bwd(grad_out, go_cstride, grad_in, gi_cstride, accumulate, B, H, W, C,
-                               static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_upsample_bwd(grad_out, go_cstride, grad_in, gi_cstride, accumulate, B, H, W, C,
+                                    static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_image_grad(const void* grad_nhwc, int g_cstride, float* grad_img, int B, int H, int W, int Hp, int pad_top,
                        void* stream) {
-    if (!grad_nhwc || !grad_img || B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp) return ADAYOLO_EINVAL;
+    if (!grad_nhwc || !grad_img || bad_frame(B, H, W, Hp, pad_top)) return ADAYOLO_EINVAL;
     if (g_cstride < 4 || g_cstride % 2) return ADAYOLO_ESHAPE;
-    return launch_image_grad(grad_nhwc, g_cstride, grad_img, B, H, W, Hp, pad_top, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_image_grad(grad_nhwc, g_cstride, grad_img, B, H, W, Hp, pad_top, static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_upsample2x(const void* in, int in_cstride, void* out, int out_cstride, int B, int H, int W, int C,
                        void* stream) {
     if (!in || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0) return ADAYOLO_EINVAL;
     if (C % 8 || in_cstride % 8 || out_cstride % 8 || in_cstride < C || out_cstride < C) return ADAYOLO_ESHAPE;
-    return launch_upsample2x(in, in_cstride, out, out_cstride, B, H, W, C, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_upsample2x(in, in_cstride, out, out_cstride, B, H, W, C, static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_detect_decode(const void* raw, int raw_cstride, float* pred, int pred_rows, int row_offset,
@@ -684,8 +673,8 @@ int adayolo_detect_decode(const void* raw, int raw_cstride, float* pred, int pre
                           void* stream) {
     if (!raw || !pred || !anchors_px || B <= 0 || ny <= 0 || nx <= 0 || na <= 0 || no < 5) return ADAYOLO_EINVAL;
     if (raw_cstride < na * no || row_offset < 0 || row_offset + na * ny * nx > pred_rows) return ADAYOLO_ESHAPE;
-    return launch_detect_decode(raw, raw_cstride, pred, pred_rows, row_offset, anchors_px, det_stride, B, ny, nx, na,
-                                no, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_detect_decode(raw, raw_cstride, pred, pred_rows, row_offset, anchors_px, det_stride, B, ny, nx, na,
+                                     no, static_cast<hipStream_t>(stream)));
 }
 
 size_t adayolo_nms_workspace_bytes(int n) {
@@ -698,8 +687,8 @@ int adayolo_nms(const float* boxes_xyxy, int n, float iou_thres, int max_det, vo
     if (n < 0 || max_det <= 0 || !keep || !num_keep || (n > 0 && (!boxes_xyxy || !workspace))) return ADAYOLO_EINVAL;
     if (n > 30000 * 4) return ADAYOLO_ESHAPE;        // LDS bit set of the scan: n/64 words
     if (!(iou_thres >= 0.0f && iou_thres <= 1.0f)) return ADAYOLO_EINVAL;
-    return launch_nms(boxes_xyxy, n, iou_thres, max_det, static_cast<unsigned long long*>(workspace), keep, num_keep,
-                      static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_nms(boxes_xyxy, n, iou_thres, max_det, static_cast<unsigned long long*>(workspace), keep, num_keep,
+                           static_cast<hipStream_t>(stream)));
 }
 
 static int detloss_check(const adayolo_loss_args* a, bool bwd) {
@@ -719,13 +708,13 @@ static int detloss_check(const adayolo_loss_args* a, bool bwd) {
 int adayolo_detloss_fwd(const adayolo_loss_args* args, void* stream) {
     const int rc = detloss_check(args, false);
     if (rc != ADAYOLO_OK) return rc;
-    return launch_detloss_fwd(*args, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_detloss_fwd(*args, static_cast<hipStream_t>(stream)));
 }
 
 int adayolo_detloss_bwd(const adayolo_loss_args* args, void* stream) {
     const int rc = detloss_check(args, true);
     if (rc != ADAYOLO_OK) return rc;
-    return launch_detloss_bwd(*args, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAYOLO_OK : ADAYOLO_ELAUNCH;
+    return code(launch_detloss_bwd(*args, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -21,19 +21,12 @@
 // distinct 16-byte bank groups, for every tap.
 // Numerics: h is rounded to bf16 exactly as the stand-alone 1x1 layer stores it; both GEMMs accumulate in fp32 over k in the
 // order the stand-alone kernels use.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace adayolo {
 namespace bnk {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
 #ifdef ADAYOLO_MEASURE
@@ -42,32 +35,6 @@ __device__ unsigned long long g_stamp[4096 * 8];
 #else
 #define BN_STAMP(k) do { } while (0)
 #endif
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-__device__ __forceinline__ void dma16(unsigned long long gaddr, void* l) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)gaddr, (lds_ptr_t)l, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned long long sel(bool ok, unsigned long long p, unsigned long long z) {
-    const unsigned long long m = ok ? ~0ull : 0ull;
-    return (p & m) | (z & ~m);
-}
-__device__ __forceinline__ void barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int C = 256, CH = 128;             // block channels, hidden channels
 constexpr int TS = 16, PS = TS + 2, NP = PS * PS;      // tile side, patch side, patch pixels (324)
@@ -79,7 +46,6 @@ constexpr int kHc = NP * kRow;               // one 64-channel chunk of the h pa
 constexpr int kH = 2 * kHc;                  // 82,944
 constexpr int kWt = C * kRow;                // one W2 k-tile: 256 rows x 128 B = 32 KB
 constexpr int kWring = kH;                   // W2 ring offset
-constexpr int kEpiPitch = 144;
 constexpr int kEpi = 8 * 128 * kEpiPitch;    // 147,456: epilogue staging, overlays h + ring
 constexpr int kSmem = kWring + 2 * kWt;      // 148,480 (>= 2 * kBufA = 131,072 and >= kEpi)
 constexpr int NXI = (NP + 7) / 8;            // 41 LDS-DMA instructions stage the 324 patch rows of a k-tile
@@ -373,8 +339,8 @@ __global__ __launch_bounds__(512) void k_bneck(const BneckArgs a) {
             for (int it = 0; it < 4; ++it)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x2_pk s = f32x2_pk{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
-                                       f32x2_pk{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
+                    const f32x2 s = f32x2{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
+                                    f32x2{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
                     v[it][j] = pack_bf16x2(s.x, s.y);
                 }
 #pragma unroll

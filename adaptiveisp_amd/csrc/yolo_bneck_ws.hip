@@ -18,7 +18,7 @@
 // ONE workgroup computes ALL output channels of its pixels (8 waves = NPG pixel groups of 4 tile rows x NCG channel groups of
 // 32): the patch and h are staged once per pixel, not once per 64-channel chunk as the stand-alone 3x3 does.
 // Both GEMMs accumulate in fp32 over k in the order the stand-alone kernels use.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include <type_traits>
 #ifndef BWS_PRIO
 #define BWS_PRIO 1          // waves 0-3 at priority 2 (yolo_conv_ws.hip's arrangement); 0: all waves equal (measurement)
@@ -26,27 +26,6 @@
 
 namespace adayolo {
 namespace bws {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr unsigned kOOB = 0xFFFFFFFFu;
-constexpr unsigned kRecords = 0xFFFFFF00u;
-constexpr unsigned kDescFlags = 0x00020000u;
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_pk{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ void barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 struct BwsArgs {
     const unsigned short* x; int x_cs;
@@ -184,7 +163,7 @@ __global__ __launch_bounds__(512) void k_bneck_ws(const BwsArgs a) {
         // most the previous tile's NST stores are outstanding.
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::NST) : "memory");
         BWS_T(0);                                        // (stamps: 0 = wait for the patch, 1 = barrier A, 2 = stage B, 3 = barrier B, 4 = patch issue,
-        barrier();                                       // A: patch(t) is in LDS (and, first tile: W1 / biases are)
+        barrier_lgkm();                                       // A: patch(t) is in LDS (and, first tile: W1 / biases are)
         BWS_T(1);                                        //  5 = stage C, 6 = residual + SiLU + barrier C, 7 = rows + stores)
 
         // ---- B: h = SiLU(b1 + W1 x) on the patch, on v_mfma_f32_16x16x32_bf16: unit u = (16 patch pixels g, 16 hidden channels
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(512) void k_bneck_ws(const BwsArgs a) {
             }
         }
         BWS_T(2);
-        barrier();                                       // B: h is complete; nobody reads the x patch any more
+        barrier_lgkm();                                       // B: h is complete; nobody reads the x patch any more
         BWS_T(3);
         // the next tile's patch is requested INSIDE stage C, one DMA instruction behind every NSTEP / NP-th MFMA step: issued
         // in one burst here the six instructions hold the wave for ~1.9k cycles (the CU's DMA path takes ~24 B/clk: stamps,
@@ -330,12 +309,12 @@ __global__ __launch_bounds__(512) void k_bneck_ws(const BwsArgs a) {
             unsigned char* const wr = obuf + pxl * G::kOutPitch + (cg * 32 + 4 * fq) * 2;
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
-                const f32x2_pk y0 = silu_pk(f32x2_pk{acc[pf][4 * qd], acc[pf][4 * qd + 1]});
-                const f32x2_pk y1 = silu_pk(f32x2_pk{acc[pf][4 * qd + 2], acc[pf][4 * qd + 3]});
+                const f32x2 y0 = silu_pk(f32x2{acc[pf][4 * qd], acc[pf][4 * qd + 1]});
+                const f32x2 y1 = silu_pk(f32x2{acc[pf][4 * qd + 2], acc[pf][4 * qd + 3]});
                 *reinterpret_cast<u32x2*>(wr + 8 * qd * 2) = u32x2{pack_bf16x2(y0.x, y0.y), pack_bf16x2(y1.x, y1.y)};
             }
         }
-        barrier();                                       // C: the output tile is complete (and every wave is done with h)
+        barrier_lgkm();                                       // C: the output tile is complete (and every wave is done with h)
         BWS_T(6);
 #pragma unroll
         for (int it = 0; it < G::NST; ++it) {
@@ -343,8 +322,8 @@ __global__ __launch_bounds__(512) void k_bneck_ws(const BwsArgs a) {
             u32x4 v = *reinterpret_cast<const u32x4*>(obuf + pxl * G::kOutPitch + chunk * 16);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const f32x2_pk s = f32x2_pk{__uint_as_float(v[j] << 16), __uint_as_float(v[j] & 0xFFFF0000u)} +
-                                   f32x2_pk{__uint_as_float(rv[it][j] << 16), __uint_as_float(rv[it][j] & 0xFFFF0000u)};
+                const f32x2 s = f32x2{__uint_as_float(v[j] << 16), __uint_as_float(v[j] & 0xFFFF0000u)} +
+                                f32x2{__uint_as_float(rv[it][j] << 16), __uint_as_float(rv[it][j] & 0xFFFF0000u)};
                 v[j] = pack_bf16x2(s.x, s.y);
             }
             __builtin_amdgcn_raw_buffer_store_b128(v, rsO, ovoff[it], 0, 2);       // nt; a masked pixel is out of range: dropped

@@ -2,6 +2,7 @@
 // (alone or with the next block's 1x1 fused) and 256 x 128 tiles of yolo_conv_pp128.hip — as work items of ONE launch.
 // The two tile bodies are compiled into this translation unit under their own namespaces (the launch-per-layer kernels of
 // the two files are untouched).
+#include "yolo_device.h"      // ahead of the renaming macros below: nothing in it is renamed
 #define ADAYOLO_TILE_ONLY
 #define pp ppc
 #include "yolo_conv_pp.hip"
@@ -14,8 +15,6 @@
 namespace adayolo {
 namespace chain {
 
-using ppc::barrier;
-using ppc::wait_vm;
 constexpr int kSmemChain = kChainSmem;
 // the scheduler words sit behind BOTH tile bodies' LDS (ring / epilogue overlay + bias): a change to a tile's pitch, BN or ring
 // must move kChainSchedOff with it
@@ -177,7 +176,6 @@ static hipError_t launch_chain(const ChainArgs& c, int grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-
 }  // namespace chain
 
 // Persistent chain of 256 x 256-tile layers (k_conv_chain): ONE kernel node; the counters at the head of the workspace are zero
@@ -186,7 +184,6 @@ hipError_t launch_conv_chain(const ChainArgs& c, int grid, hipStream_t s) {
     if (!c.ws || c.total <= 0 || grid <= 0 || c.ndone < 0) return hipErrorInvalidValue;
     return chain::launch_chain(c, grid < c.total ? grid : c.total, s);
 }
-
 
 #ifdef ADAYOLO_CHAIN_STAMPS
 // measurement helper (not part of the ABI): reads and clears the chain kernels' phase accumulators

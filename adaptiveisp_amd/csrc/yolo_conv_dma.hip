@@ -14,53 +14,15 @@
 //     swizzle applied on both sides: lane (row r, slot j) fetches k-chunk j ^ ((r >> 1) & 7) and fragment
 //     reads look up chunk c at slot c ^ ((r >> 1) & 7): the 16 rows of a ds_read_b128 group then cover
 //     all sixteen 16-B slots of the 256-B bank row.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 
 namespace adayolo {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
 namespace dma {
 
 constexpr int kThreads = 256;
 constexpr int BK = 64;                 // bf16 per tile row = 128 B = 8 chunks of 16 B
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-typedef __attribute__((ext_vector_type(2))) __bf16 hw_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float hw_f32x2;
-// round-to-nearest-even pair conversion on the hardware unit (v_cvt_pk_bf16_f32) instead of ~8 integer VALU ops
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(hw_f32x2{lo, hi}, hw_bf16x2));
-}
-__device__ __forceinline__ float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_and_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ void dma16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)l, 16, 0, 0);
-}
 
 template <int BM, int BN, int WM, int WN, int STAGES>
 __global__ __launch_bounds__(kThreads) void k_conv_igemm_dma(const ConvArgs a) {

@@ -15,28 +15,12 @@
 //   * transposes the bf16 result through the (dead) activation tile and stores whole 512-byte pixel rows, non-temporal.
 // Restrictions (hipErrorInvalidValue otherwise, the caller keeps its ring kernel): ksize 1, stride 1, no residual,
 // Cin in {256, 512}, Cout % 256 == 0.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 
 namespace adayolo {
 namespace k1 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void dma16(unsigned long long gaddr, void* l) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)gaddr, (lds_ptr_t)l, 16, 0, 0);
-}
-__device__ __forceinline__ void barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 constexpr int BM = 128, BN = 256;
 constexpr int kOutPitch = BN * 2 + 16;               // bytes per pixel row of the output tile in LDS (2-way write conflicts at most)
@@ -89,7 +73,7 @@ __global__ __launch_bounds__(512) void k_conv_k1(const ConvArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[pf][e] = 0.0f;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    barrier();
+    barrier_lgkm();
 
     // ---- K / 16 steps x 4 pixel fragments; the fragments of step kk + 1 are requested before the MFMAs of step kk
     const unsigned char* abase = smem + r * G::RB;
@@ -110,7 +94,7 @@ __global__ __launch_bounds__(512) void k_conv_k1(const ConvArgs a) {
         for (int pf = 0; pf < 4; ++pf) acc[pf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk], af[kk & 1][pf], acc[pf], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    barrier();                                            // every wave has read the activation tile: the output tile overlays it
+    barrier_lgkm();                                            // every wave has read the activation tile: the output tile overlays it
 
     // ---- epilogue: D[row = channel][col = pixel]; lane holds pixel r and channels 8 qd + 4 fq + (0..3) of its wave's 32
 #pragma unroll
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(512) void k_conv_k1(const ConvArgs a) {
             *reinterpret_cast<u32x2*>(wr + 8 * qd * 2) = u32x2{lo, hi};
         }
     }
-    barrier();
+    barrier_lgkm();
     // 128 px x 512 B: a lane takes 16 B (8 channels); one wave instruction = two whole pixel rows
 #pragma unroll
     for (int it = 0; it < BM * (BN / 8) / 512; ++it) {

@@ -27,7 +27,7 @@
 // And: the four waves of a group issuing their two pieces behind DIFFERENT MFMAs of a section (wave w behind the w-th and
 // (w+4)-th, a scalar compare + branch per slot) instead of all behind the 1st and the 4th: 78 vs 70 us — the extra states between
 // MFMAs cost more than the texture-address queue they were meant to spare.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include "yolo_chain.h"
 #ifndef PP_PRIO_MODE
 #define PP_PRIO_MODE 0      // 0: s_setprio 1 around every MFMA section (default); 1: no priority; 2: static priority for the second wave group (measurement builds)
@@ -47,11 +47,6 @@
 namespace adayolo {
 namespace pp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
 #ifdef ADAYOLO_MEASURE
 __device__ unsigned long long g_stamp[4096 * 8];     // ABL 7: per-workgroup s_memtime stamps (measurement build)
@@ -68,48 +63,10 @@ __device__ unsigned long long g_stamp[8];
 #define PP_STAMP(k) do { if (ABL == 7 && threadIdx.x == 0 && blockIdx.x < 4096) g_stamp[blockIdx.x * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
 #endif
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {      // round-to-nearest-even: v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-__device__ __forceinline__ void dma16(unsigned long long gaddr, void* l) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)gaddr, (lds_ptr_t)l, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned long long sel(bool ok, unsigned long long p, unsigned long long z) {
-    const unsigned long long m = ok ? ~0ull : 0ull;
-    return (p & m) | (z & ~m);
-}
-__device__ __forceinline__ void barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int kRow = BK * 2;                 // bytes per tile row
 constexpr int kTile = 256 * kRow;            // one operand k-tile: 32 KB
 constexpr int kBuf = 2 * kTile;              // A + W of one k-tile
-constexpr int kEpiPitch = 144;                // bytes per pixel row of a wave's private epilogue region (64 ch + pad)
 constexpr int kEpi = 8 * 128 * kEpiPitch;     // 8 waves x 128 px: 144 KB, overlays the (finished) ring
 constexpr int kSmem = (kEpi > 2 * kBuf ? kEpi : 2 * kBuf) + BN * 4;   // + bias
 
@@ -465,8 +422,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
                 for (int it = 0; it < 4; ++it)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const f32x2_pk x = f32x2_pk{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
-                                           f32x2_pk{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
+                        const f32x2 x = f32x2{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
+                                        f32x2{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
                         v[it][j] = pack_bf16x2(x.x, x.y);
                     }
             }

@@ -24,7 +24,7 @@
 // with the six DMA pieces issued in the LOAD section so that the MFMA section is MFMAs only: 88 us (a piece costs the issuing
 // wave ~150 cycles there, four waves at once). The barriers are not what holds this kernel; the operand stream is
 // (profiles/round2_conv_pp_ablation.txt).
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include "yolo_chain.h"
 #ifndef PP_PRIO_MODE
 #define PP_PRIO_MODE 0      // 0: s_setprio 1 around every MFMA section (default); 1: no priority; 2: static priority for the second wave group (measurement builds)
@@ -34,51 +34,13 @@
 namespace adayolo {
 namespace pp128 {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {      // round-to-nearest-even: v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-__device__ __forceinline__ void dma16(unsigned long long gaddr, void* l) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)gaddr, (lds_ptr_t)l, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned long long sel(bool ok, unsigned long long p, unsigned long long z) {
-    const unsigned long long m = ok ? ~0ull : 0ull;
-    return (p & m) | (z & ~m);
-}
-__device__ __forceinline__ void barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int BM = 256, BN = 128, BK = 64;
 constexpr int kRow = BK * 2;                  // bytes per tile row
 constexpr int kATile = BM * kRow;             // 32 KB
 constexpr int kBuf = (BM + BN) * kRow;        // one k-tile: 48 KB
 constexpr int kRing = 3 * kBuf;               // 144 KB
-constexpr int kEpiPitch = 144;                // bytes per pixel row of a wave's private epilogue region (64 ch + pad)
 constexpr int kSmem = kRing + BN * 4 + 16;    // + bias + the split-K ticket; the epilogue (8 x 64 x 144 B = 72 KB) overlays the finished ring
 
 struct KPos {                                 // wave-uniform position of a k-tile

@@ -25,24 +25,17 @@
 //
 // Restrictions (the launcher falls back otherwise): Cin % 32 == 0, Cout % 128 == 0, K >= 96, tensors addressable with
 // 32-bit byte offsets, Ho*Wo > 1, Wo > 1.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace adayolo {
 namespace pq {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 template <int N> using IC = std::integral_constant<int, N>;
 
 constexpr int BN = 128, BK = 32;
 constexpr int kRow = BK * 2;                  // 64 bytes per tile row
-constexpr int kEpiPitch = 144;                // bytes per pixel row of a wave's private epilogue region (64 ch + pad)
 // MI = 32-pixel fragments per wave: 4 -> 256 px tile (24 KB per k-tile, 72 KB ring), 2 -> 128 px tile (16 KB, 48 KB): the
 // small maps (8x23x40: 29 tiles of 256 px) get twice the workgroups. (A 64 px tile — MI = 1, 82 registers, four workgroups
 // per CU — was measured and dropped: slower on every layer, 16 vs 13 us on 1024 -> 512 @ 8x23x40, four MFMAs per barrier.)
@@ -56,18 +49,8 @@ template <int MI> struct Geo {
     static constexpr int NA = MI;                              // activation DMA pieces per wave and k-tile (16 rows each)
     static constexpr int NP = MI + 2;                          // ... + 2 weight pieces
 };
-constexpr unsigned kOOB = 0xFFFFFFFFu;
-constexpr unsigned kRecords = 0xFFFFFF00u;
-constexpr unsigned kDescFlags = 0x00020000u;
 
 __device__ __forceinline__ void fence() { __builtin_amdgcn_sched_barrier(0); }
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_pk{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 #define PQ_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 // ABL (measurement builds): 0 the kernel, 1 no LDS-DMA in the k-loop, 2 no epilogue
@@ -307,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_pq(const ConvArgs a) {
             for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
-                    f32x2_pk x0 = {acc[ni][mi][4 * qd], acc[ni][mi][4 * qd + 1]}, x1 = {acc[ni][mi][4 * qd + 2], acc[ni][mi][4 * qd + 3]};
+                    f32x2 x0 = {acc[ni][mi][4 * qd], acc[ni][mi][4 * qd + 1]}, x1 = {acc[ni][mi][4 * qd + 2], acc[ni][mi][4 * qd + 3]};
                     if (kSilu) { x0 = silu_pk(x0); x1 = silu_pk(x1); }
                     *reinterpret_cast<u32x2*>(wr + mi * 32 * kEpiPitch + (ni * 32 + 8 * qd) * 2) =
                         u32x2{pack_bf16x2(x0.x, x0.y), pack_bf16x2(x1.x, x1.y)};
@@ -330,8 +313,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_pq(const ConvArgs a) {
                 for (int it = 0; it < 4; ++it)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const f32x2_pk x = f32x2_pk{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
-                                           f32x2_pk{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
+                        const f32x2 x = f32x2{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
+                                        f32x2{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
                         v[it][j] = pack_bf16x2(x.x, x.y);
                     }
             }

@@ -5,39 +5,13 @@
 // loads, in ONE DMA round, (a) the input patch of its output tile (stride 1 or 2, 1-px halo) and (b) ALL nine
 // weight taps of its output channels, then runs the 9 x Cin/16 MFMA steps back to back from LDS and stores.
 // Several workgroups per CU hide the single load latency. HBM traffic = input once (+halo) + output once.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include <type_traits>
 
 namespace adayolo {
 namespace smallk {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-typedef __attribute__((ext_vector_type(2))) __bf16 hw_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float hw_f32x2;
-// round-to-nearest-even pair conversion on the hardware unit (v_cvt_pk_bf16_f32) instead of ~8 integer VALU ops
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(hw_f32x2{lo, hi}, hw_bf16x2));
-}
-__device__ __forceinline__ float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-__device__ __forceinline__ void dma16(unsigned long long gaddr, void* l) {
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)gaddr, (lds_ptr_t)l, 16, 0, 0);
-}
 
 // swizzle key of a tile row whose rows are CIN*2 bytes (64 B -> 4 rows per 256-B bank row, 128 B -> 2)
 template <int CIN>

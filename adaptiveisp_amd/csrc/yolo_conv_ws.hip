@@ -19,35 +19,16 @@
 // tiles; the rows of tile i - 1 leave in the SiLU phase of tile i). Per tile 9.8k cycles against 9.4k here (Cin = 64): side by
 // side the two phases take 3.5k each (alone 3.0k and 2.8k), the patch issue (1.3k) lands in front of a group's MFMAs, and the
 // within-tile skew below already overlaps one SiLU phase of two.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include <type_traits>
 
 namespace adayolo {
 namespace ws {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int TH = 16, TW = 16, PH = TH + 2, PW = TW + 2, PROWS = PH * PW;   // 18 x 18 = 324 patch pixels
 constexpr int BN = 64;                               // output channels per workgroup
-constexpr int kOutPitch = 144;                       // bytes per pixel row of the output tile (64 ch + pad)
-constexpr int kOutBytes = TH * TW * kOutPitch;       // 36 KB
-constexpr unsigned kOOB = 0xFFFFFFFFu;
-constexpr unsigned kRecords = 0xFFFFFF00u;
-constexpr unsigned kDescFlags = 0x00020000u;
+constexpr int kOutBytes = TH * TW * kEpiPitch;       // 36 KB
 
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_pk{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ void barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 // swizzle key of a patch pixel: a function of its x coordinate in the 18-wide patch, (x >> 1) & (chunks per row - 1).
 // A ds_read_b128 lane group holds pixels x in {0-3, 12-15} of one tile row and {4-11} of the next (+ the tap's kw): keyed
 // by the linear patch row, rows 16 apart share a bank slot (2-way conflicts on every fragment read: the LDS time doubles
@@ -165,7 +146,7 @@ __global__ __launch_bounds__(512) void k_conv_ws(const ConvArgs a, const int til
         // plain vmcnt(0) here waits for the previous tile's STORES to be acknowledged by HBM.
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPMIN + 4) : "memory");
         WS_T(0);
-        barrier();
+        barrier_lgkm();
         WS_T(1);
         f32x16 acc[2];                                // start at the bias: channels 8 qd + 4 fq + (0..3) of the wave's 32
 #pragma unroll
@@ -241,27 +222,27 @@ __global__ __launch_bounds__(512) void k_conv_ws(const ConvArgs a, const int til
 #pragma unroll
         for (int pf = 0; pf < 2; ++pf) {
             const int px = (pg * 4 + pf * 2 + ((lane & 31) >> 4)) * TW + (lane & 15);          // pixel index in the tile
-            unsigned char* const wr = obuf + px * kOutPitch + (cg * 32 + 4 * fq) * 2;
+            unsigned char* const wr = obuf + px * kEpiPitch + (cg * 32 + 4 * fq) * 2;
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
-                const f32x2_pk x0 = silu_pk(f32x2_pk{acc[pf][4 * qd], acc[pf][4 * qd + 1]});
-                const f32x2_pk x1 = silu_pk(f32x2_pk{acc[pf][4 * qd + 2], acc[pf][4 * qd + 3]});
+                const f32x2 x0 = silu_pk(f32x2{acc[pf][4 * qd], acc[pf][4 * qd + 1]});
+                const f32x2 x1 = silu_pk(f32x2{acc[pf][4 * qd + 2], acc[pf][4 * qd + 3]});
                 *reinterpret_cast<u32x2*>(wr + 8 * qd * 2) = u32x2{pack_bf16x2(x0.x, x0.y), pack_bf16x2(x1.x, x1.y)};
             }
         }
         WS_T(3);
-        barrier();                                   // every wave has read patch(t) (its buffer takes patch(t + 2)) and written its
+        barrier_lgkm();                                   // every wave has read patch(t) (its buffer takes patch(t + 2)) and written its
         stage_patch(t + 2 * nwg_per_chunk, pb);      // part of the output tile
         WS_T(4);
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int px = (tid >> 3) + 64 * it;
-            u32x4 v = *reinterpret_cast<const u32x4*>(obuf + px * kOutPitch + (tid & 7) * 16);
+            u32x4 v = *reinterpret_cast<const u32x4*>(obuf + px * kEpiPitch + (tid & 7) * 16);
             if (RES) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x2_pk x = f32x2_pk{__uint_as_float(v[j] << 16), __uint_as_float(v[j] & 0xFFFF0000u)} +
-                                       f32x2_pk{__uint_as_float(rv[it][j] << 16), __uint_as_float(rv[it][j] & 0xFFFF0000u)};
+                    const f32x2 x = f32x2{__uint_as_float(v[j] << 16), __uint_as_float(v[j] & 0xFFFF0000u)} +
+                                    f32x2{__uint_as_float(rv[it][j] << 16), __uint_as_float(rv[it][j] & 0xFFFF0000u)};
                     v[j] = pack_bf16x2(x.x, x.y);
                 }
             }

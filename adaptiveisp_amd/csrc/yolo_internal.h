@@ -1,4 +1,5 @@
-// Shared between the translation units of libadayolo.so.
+// Host / launcher interface shared between the translation units of libadayolo.so (what the kernels share on the device
+// side — vector types, helpers, epilogue math — is yolo_device.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,6 +7,9 @@
 
 namespace adayolo {
 
+// Host code starts from `ConvArgs{}` — every member zero or its default — and sets what the entry point uses (yolo_api.hip), so
+// that a new field cannot be left uninitialised in one of them. (No default initialisers on the members below: the chain
+// kernel declares a ConvArgs it fills from its tables.)
 struct ConvArgs {
     const unsigned short* in; int in_cs;
     const unsigned short* w; const float* bias;
@@ -40,62 +44,7 @@ struct ConvArgs {
     int chain_tile = 0;
 };
 
-// (pixel, channel) of an epilogue element in the tensors it addresses: the identity, or the depth-to-space map above
-__device__ __forceinline__ void epilogue_pos(const ConvArgs& a, int m, int n, long& pix, int& nn) {
-    pix = m; nn = n;
-    if (a.d2s_c) {
-        const int b = a.sh_hw < 0 ? m : (int)(__umulhi((unsigned)m, a.magic_hw) >> a.sh_hw);
-        const int rem = m - b * (a.Ho * a.Wo);
-        const int i = a.sh_w < 0 ? rem : (int)(__umulhi((unsigned)rem, a.magic_w) >> a.sh_w);
-        const int j = rem - i * a.Wo;
-        const int p = n / a.d2s_c;
-        nn = n - p * a.d2s_c;
-        pix = ((long)(b * 2 * a.Ho + 2 * i + (p >> 1))) * (2 * a.Wo) + 2 * j + (p & 1);
-    }
-}
-
-// Epilogue math on channel pairs: packed fp32 (v_pk_add/mul_f32 do two channels per issue slot; the two transcendentals
-// stay per element) — the conv epilogues are VALU-bound on exactly this (128 SiLUs per lane in the 256x256 kernel).
-typedef float f32x2_pk __attribute__((ext_vector_type(2)));
-// eight bf16 values of an epilogue row: silu of each, rounded back to bf16 (the training forward's second output)
-__device__ __forceinline__ f32x2_pk silu_pk(f32x2_pk x);
-__device__ __forceinline__ unsigned silu_bf16x2(unsigned v) {
-    typedef __bf16 bf16x2_pk __attribute__((ext_vector_type(2)));
-    const f32x2_pk y = silu_pk(f32x2_pk{__uint_as_float(v << 16), __uint_as_float(v & 0xFFFF0000u)});
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(y, bf16x2_pk));
-}
-// g * silu'(p) on a bf16 pair, rounded back to bf16 — THE formula of the backward (k_silu_bwd and the conv epilogues that
-// absorb it must agree bit for bit, hence the explicit fma: nothing is left to contraction).
-// silu'(p) = s + p s (1 - s), s = sigmoid(p)
-__device__ __forceinline__ float dsilu_f32(float g, float p) {
-    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * p));
-    return g * __builtin_fmaf(p * s, 1.0f - s, s);
-}
-__device__ __forceinline__ unsigned dsilu_bf16x2(unsigned g, unsigned p) {
-    typedef __bf16 bf16x2_pk __attribute__((ext_vector_type(2)));
-    const f32x2_pk y = {dsilu_f32(__uint_as_float(g << 16), __uint_as_float(p << 16)),
-                        dsilu_f32(__uint_as_float(g & 0xFFFF0000u), __uint_as_float(p & 0xFFFF0000u))};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(y, bf16x2_pk));
-}
-__device__ __forceinline__ f32x2_pk silu_pk(f32x2_pk x) {
-    const f32x2_pk u = x * -1.44269504088896341f;
-    f32x2_pk e = {__builtin_amdgcn_exp2f(u.x), __builtin_amdgcn_exp2f(u.y)};
-    e = e + 1.0f;
-    const f32x2_pk r = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-    return x * r;
-}
-// four consecutive channels: + bias, SiLU (compile-time), round to bf16 (v_cvt_pk_bf16_f32) -> two packed words
-template <bool SILU>
-__device__ __forceinline__ void bias_act_pack4(float a0, float a1, float a2, float a3, const float4 b, unsigned& lo, unsigned& hi) {
-    typedef __bf16 bf16x2_pk __attribute__((ext_vector_type(2)));
-    f32x2_pk x0 = f32x2_pk{a0, a1} + f32x2_pk{b.x, b.y};
-    f32x2_pk x1 = f32x2_pk{a2, a3} + f32x2_pk{b.z, b.w};
-    if (SILU) { x0 = silu_pk(x0); x1 = silu_pk(x1); }
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(x0, bf16x2_pk));
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x1, bf16x2_pk));
-}
-
-// ---- persistent chain (yolo_conv_pp.hip: k_conv_chain): several consecutive layers of the 256 x 256 kernel's tiles in ONE launch.
+// ---- persistent chain (yolo_conv_chain.hip: k_conv_chain): consecutive layers' tiles (256 x 256, 256 x 128) in ONE launch.
 // One work item = one tile of one layer; the tables are built on the host (yolo_api.hip: adayolo_conv_chain_prepare).
 // Workspace (device, caller-owned; the byte offsets are multiples of 64):
 //   [0, 64)            int head (next item to hand out), int err (!= 0: a bounded wait of THIS launch gave up: item + 1), int exit

@@ -17,7 +17,7 @@
 // per-match one that recomputes CIoU with its analytic gradient and adds the box / class terms (duplicates of a cell
 // are summed in match order by the first of them). The maps are the detector's own bf16 NHWC buffers — no fp32
 // [B, na, ny, nx, no] copies in either direction.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 
 namespace adayolo {
 namespace dl {
@@ -25,13 +25,14 @@ namespace dl {
 constexpr int kThreads = 256;
 constexpr float kEps = 1e-7f;
 
-__device__ __forceinline__ float bf(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short to_bf(float f) {            // round to nearest even (as torch's .to(bfloat16))
+// round to nearest even as torch's .to(bfloat16): yolo_device.h's f32_to_bf16 plus the NaN case (a NaN stays a quiet NaN)
+__device__ __forceinline__ unsigned short to_bf(float f) {
     unsigned u = __float_as_uint(f);
     if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (unsigned short)((u >> 16) | 0x40u);
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
+// (libm expf and a true division, as the loss it reproduces: yolo_train.hip's sigmoidf_ is the conv epilogues' exp2 / rcp form)
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 // F.binary_cross_entropy_with_logits(x, t, pos_weight = pw): (1 - t) x + (1 + (pw - 1) t) (log1p(exp(-|x|)) + max(-x, 0))
 __device__ __forceinline__ float bce(float x, float t, float pw) {
@@ -115,7 +116,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 __device__ __forceinline__ void load_box_logits(const unsigned short* cell, float lg[4]) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) lg[k] = bf(cell[k]);
+    for (int k = 0; k < 4; ++k) lg[k] = bf16_to_f32(cell[k]);
 }
 __device__ __forceinline__ float wave_sum(float v) {                    // fixed xor tree: every lane gets the sum
 #pragma unroll
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void k_detloss_fwd(const adayolo_loss_arg
         const Match m = ciou_match<false>(lg, bx[4], bx[5], bx[0], bx[1], bx[2], bx[3]);
         float s = 0.0f;
         if (a.nc > 1)
-            for (int c = lane; c < a.nc; c += 64) s += bce(bf(cell[5 + c]), c == id[4] ? a.cp : a.cn, a.cls_pw);
+            for (int c = lane; c < a.nc; c += 64) s += bce(bf16_to_f32(cell[5 + c]), c == id[4] ? a.cp : a.cn, a.cls_pw);
         s = wave_sum(s);
         // a later match of the same cell overwrites this one's objectness target (sequential index assignment)
         const bool last = !any_same(idx, id, j + 1, L.n, lane);
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void k_detloss_fwd(const adayolo_loss_arg
     float sobj = 0.0f;
     for (int c = tid; c < cells; c += kThreads) {
         const int an = c / plane, p = c - an * plane;
-        sobj += bce(bf(raw[(long)p * L.cs + an * a.no + 4]), tobj[c], a.obj_pw);
+        sobj += bce(bf16_to_f32(raw[(long)p * L.cs + an * a.no + 4]), tobj[c], a.obj_pw);
     }
     sbox = block_sum(sbox, red);
     scls = block_sum(scls, red);
@@ -231,10 +232,9 @@ __global__ __launch_bounds__(kThreads) void k_detloss_bwd_dense(const adayolo_lo
         o[k] = 0;
         if (ch < a.na * a.no) {
             const int an = ch / a.no;
-            if (ch - an * a.no == 4) o[k] = to_bf(scale * bce_grad(bf(raw[ch]), tobj[an * plane + p], a.obj_pw));
+            if (ch - an * a.no == 4) o[k] = to_bf(scale * bce_grad(bf16_to_f32(raw[ch]), tobj[an * plane + p], a.obj_pw));
         }
     }
-    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
     const u32x4 v = {o[0] | ((unsigned)o[1] << 16), o[2] | ((unsigned)o[3] << 16), o[4] | ((unsigned)o[5] << 16),
                      o[6] | ((unsigned)o[7] << 16)};
     *reinterpret_cast<u32x4*>(static_cast<unsigned short*>(L.grad) + ((long)b * plane + p) * L.grad_cs + c0) = v;
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void k_detloss_bwd_match(const adayolo_lo
         unsigned short* gcell = grad + off * L.grad_cs + id[1] * a.no;
         float lg[4], gb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         load_box_logits(cell, lg);
-        const float x0 = lane < a.nc ? bf(cell[5 + lane]) : 0.0f, x1 = lane + 64 < a.nc ? bf(cell[5 + lane + 64]) : 0.0f;
+        const float x0 = lane < a.nc ? bf16_to_f32(cell[5 + lane]) : 0.0f, x1 = lane + 64 < a.nc ? bf16_to_f32(cell[5 + lane + 64]) : 0.0f;
         float g0 = 0.0f, g1 = 0.0f;
         for (int base = j; base < L.n; base += 64) {                    // the cell's matches in match order
             const int j2 = base + lane;

@@ -1,28 +1,8 @@
 // Detector-side kernels that are not the generic conv: the fused ISP->detector stem, nearest 2x
 // up-sampling into a concat slice, and the Detect-head decode. gfx950 only.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 
 namespace adayolo {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-typedef __attribute__((ext_vector_type(2))) __bf16 hw_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float hw_f32x2;
-// round-to-nearest-even pair conversion on the hardware unit (v_cvt_pk_bf16_f32) instead of ~8 integer VALU ops
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(hw_f32x2{lo, hi}, hw_bf16x2));
-}
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Stem: letterbox + Conv(3->32, k3 s1 p1) + SiLU, planar fp32 in, NHWC bf16 out.
@@ -70,7 +50,7 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ img, con
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int k = 8 * g + e;
-            h[e] = (k < 27) ? f2bf(w[ch * 27 + k]) : (unsigned short)0;
+            h[e] = (k < 27) ? f32_to_bf16(w[ch * 27 + k]) : (unsigned short)0;
         }
         u32x4 pk = {(unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16),
                     (unsigned)h[4] | ((unsigned)h[5] << 16), (unsigned)h[6] | ((unsigned)h[7] << 16)};
@@ -89,7 +69,7 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ img, con
         float a[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = t0[off[e]];
-        u32x4 pk = {pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(a[4], a[5]), pack2(a[6], a[7])};
+        u32x4 pk = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(a[4], a[5]), pack_bf16x2(a[6], a[7])};
         const bf16x8 af = __builtin_bit_cast(bf16x8, pk);
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const f32x4 d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0], af, z, 0, 0, 0);
@@ -101,7 +81,7 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ img, con
                 v[i] = d0[i] + bv[i]; v[4 + i] = d1[i] + bv[4 + i];
                 if (act && !pre) { v[i] = silu(v[i]); v[4 + i] = silu(v[4 + i]); }
             }
-            u32x4 o = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+            u32x4 o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
             if (pre) {      // training forward: keep the bf16 pre-activation, activate THAT value (adayolo_silu_fwd's arithmetic)
                 *reinterpret_cast<u32x4*>(pre + (((long)b * Hp + gy) * W + gx) * pre_cs + 8 * g) = o;
                 if (act) {
@@ -138,7 +118,7 @@ __global__ __launch_bounds__(256) void k_letterbox_pack(const float* __restrict_
         const float* src = img + (long)b * 3 * plane + (long)sy * W + gx;
         r = src[0]; g = src[plane]; bl = src[2 * plane];
     }
-    const u32x4 o = {pack2(r, g), pack2(bl, 0.0f), 0u, 0u};
+    const u32x4 o = {pack_bf16x2(r, g), pack_bf16x2(bl, 0.0f), 0u, 0u};
     *reinterpret_cast<u32x4*>(out + (((long)b * Hp + gy) * W + gx) * out_cs) = o;
 }
 
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(256) void k_detect_decode(const unsigned short* __r
     float* dst = pred + (b * pred_rows + row_offset + (long)an * ny * nx) * no;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < per_map; i += gridDim.x * 256) {
         const int cell = i / no, j = i - cell * no;
-        const float t = bf2f(src[(long)cell * raw_cs + j]);
+        const float t = bf16_to_f32(src[(long)cell * raw_cs + j]);
         const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * t));
         float v = s;
         if (j < 4) {
@@ -229,7 +209,6 @@ __global__ __launch_bounds__(256) void k_detect_decode_tiled(const unsigned shor
                                                              int ny, int nx, int na, int no) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
     unsigned short* l16 = reinterpret_cast<unsigned short*>(dsm);          // [na][DC][no]
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
     const int ncell = ny * nx;
     const int cell0 = blockIdx.x * DC;
     const int nc = min(DC, ncell - cell0);
@@ -275,7 +254,7 @@ __global__ __launch_bounds__(256) void k_detect_decode_tiled(const unsigned shor
         const unsigned short* lp = l16 + (an * DC + cl) * no;
         float sg[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) sg[u] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * bf2f(lp[u])));
+        for (int u = 0; u < 4; ++u) sg[u] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * bf16_to_f32(lp[u])));
         float* bo = boxf + (an * DC + cl) * 4;
         bo[0] = (sg[0] * 2.0f + ((float)x - 0.5f)) * det_stride;
         bo[1] = (sg[1] * 2.0f + ((float)y - 0.5f)) * det_stride;
@@ -291,7 +270,7 @@ __global__ __launch_bounds__(256) void k_detect_decode_tiled(const unsigned shor
             const uint2 p = *reinterpret_cast<const uint2*>(la + 8 * e4);
             const float t[4] = {__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xFFFF0000u),
                                 __uint_as_float(p.y << 16), __uint_as_float(p.y & 0xFFFF0000u)};
-            f32x4v o;
+            f32x4 o;
 #pragma unroll
             for (int u = 0; u < 4; ++u) o[u] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * t[u]));
             const int cl = (int)(((float)(4 * e4) + 0.5f) * inv_no), j0 = 4 * e4 - cl * no;
@@ -303,7 +282,7 @@ __global__ __launch_bounds__(256) void k_detect_decode_tiled(const unsigned shor
                     if (j < 4) o[u] = boxf[(an * DC + cl + wrp) * 4 + j];
                 }
             }
-            __builtin_nontemporal_store(o, reinterpret_cast<f32x4v*>(dst + 4 * e4));
+            __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dst + 4 * e4));
         }
     }
 }

@@ -23,27 +23,11 @@
 // transcendentals). A persistent form that requests the next tile's patch under phase B was measured SLOWER (340 vs 282 us;
 // tools/experiments/stem_down_persistent.patch).
 // Numerics: the same roundings as the two separate kernels (image and stem output rounded to bf16, fp32 accumulation).
-#include "yolo_internal.h"
+#include "yolo_device.h"
 #include <cstdlib>
 
 namespace adayolo {
 namespace sd {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-__device__ __forceinline__ float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
-}
 
 constexpr int TY = 8, TX = 16;                       // output tile of the second conv
 constexpr int SH = 2 * TY + 1, SW = 2 * TX + 1;      // stem pixels under it: 17 x 33
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(256, 4) void k_stem_down(const float* __restrict__ 
         for (int it = 0; it < NI; ++it) {
             const float r = inimg[it] ? v[it][0] : padc[it], gg = inimg[it] ? v[it][1] : padc[it], bb = inimg[it] ? v[it][2] : padc[it];
             if (tid + 256 * it < NPX)
-                *reinterpret_cast<u32x2*>(img4 + (tid + 256 * it) * 8) = u32x2{pack2(r, gg), pack2(bb, 0.0f)};
+                *reinterpret_cast<u32x2*>(img4 + (tid + 256 * it) * 8) = u32x2{pack_bf16x2(r, gg), pack_bf16x2(bb, 0.0f)};
         }
     }
 
@@ -154,7 +138,7 @@ __global__ __launch_bounds__(256, 4) void k_stem_down(const float* __restrict__ 
                     asm volatile("" : "+v"(h[kh][t][c]));
                     h[kh][t][c] = g < 3 ? h[kh][t][c] : 0.0f;
                 }
-                const u32x2 pk = {pack2(h[kh][t][0], h[kh][t][1]), pack2(h[kh][t][2], 0.0f)};
+                const u32x2 pk = {pack_bf16x2(h[kh][t][0], h[kh][t][1]), pack_bf16x2(h[kh][t][2], 0.0f)};
                 wfk[kh][t] = __builtin_bit_cast(s16x4, pk);
             }
     }

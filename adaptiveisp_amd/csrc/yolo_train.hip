@@ -10,19 +10,11 @@
 //   k_image_grad     NHWC bf16 (3 of 8 channels) -> planar fp32 [B,3,H,W] without the letterbox rows
 //   k_stem (act)     the stem without SiLU, so its pre-activation can be kept
 // All tensors NHWC bf16 with explicit channel strides (channel slices of concat buffers), 16-byte vectors.
-#include "yolo_internal.h"
+#include "yolo_device.h"
 
 namespace adayolo {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-__device__ __forceinline__ float lo_f(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float hi_f(unsigned v) { return __uint_as_float(v & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned pk(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
+// the sigmoid inside silu (yolo_device.h), v_exp / v_rcp — not yolo_loss.hip's sigmoidf, which is libm expf and a division
 __device__ __forceinline__ float sigmoidf_(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x));
 }
@@ -44,10 +36,10 @@ __global__ __launch_bounds__(256) void k_silu_fwd(const unsigned short* __restri
             const float a = lo_f(p[j]), b = hi_f(p[j]);
             float ya = a * sigmoidf_(a), yb = b * sigmoidf_(b);
             if (res) {                       // forward conv kernels round to bf16 before the shortcut add: same here
-                ya = lo_f(pk(ya, 0.f)) + lo_f(r[j]);
-                yb = lo_f(pk(yb, 0.f)) + hi_f(r[j]);
+                ya = lo_f(pack_bf16x2(ya, 0.f)) + lo_f(r[j]);
+                yb = lo_f(pack_bf16x2(yb, 0.f)) + hi_f(r[j]);
             }
-            o[j] = pk(ya, yb);
+            o[j] = pack_bf16x2(ya, yb);
         }
         *reinterpret_cast<u32x4*>(out + pix * out_cs + ch) = o;
     }
@@ -77,7 +69,7 @@ __global__ __launch_bounds__(256) void k_silu_bwd(const unsigned short* __restri
             if (accumulate) {
                 const u32x4 old = *reinterpret_cast<const u32x4*>(dst);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = pk(lo_f(g[j]) + lo_f(old[j]), hi_f(g[j]) + hi_f(old[j]));
+                for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(lo_f(g[j]) + lo_f(old[j]), hi_f(g[j]) + hi_f(old[j]));
             }
             *reinterpret_cast<u32x4*>(dst) = o;
         }
@@ -126,8 +118,8 @@ __global__ __launch_bounds__(256) void k_upsample_bwd(const unsigned short* __re
         u32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            o[j] = pk(((lo_f(a[j]) + lo_f(c[j])) + (lo_f(d[j]) + lo_f(e[j]))) + lo_f(old[j]),
-                      ((hi_f(a[j]) + hi_f(c[j])) + (hi_f(d[j]) + hi_f(e[j]))) + hi_f(old[j]));
+            o[j] = pack_bf16x2(((lo_f(a[j]) + lo_f(c[j])) + (lo_f(d[j]) + lo_f(e[j]))) + lo_f(old[j]),
+                               ((hi_f(a[j]) + hi_f(c[j])) + (hi_f(d[j]) + hi_f(e[j]))) + hi_f(old[j]));
         *reinterpret_cast<u32x4*>(dst) = o;
     }
 }
