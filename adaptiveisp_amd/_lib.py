@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_resize_u8", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_resize_u8", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -65,6 +65,10 @@ def load():
     L.adaisp_demosaic.restype = ci
     L.adaisp_unprocess.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, cu, vp]
     L.adaisp_unprocess.restype = ci
+    L.adaisp_unprocess_bayer.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, cu, ci, ctypes.c_float, ctypes.c_float, vp]
+    L.adaisp_unprocess_bayer.restype = ci
+    L.adaisp_demosaic_rects.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
+    L.adaisp_demosaic_rects.restype = ci
     sz = ctypes.c_size_t
     L.adaisp_resize_u8.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, ci, ci, vp]
     L.adaisp_resize_u8.restype = ci
@@ -329,6 +333,66 @@ def unprocess(src, desc, S, seed=0, flags=0, out=None):
         rc = L.adaisp_unprocess(src.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, int(seed) & (2 ** 64 - 1),
                                 int(flags), _stream())
     _check(rc, "adaisp_unprocess")
+    _wrote(out)
+    return out
+
+
+def _bytes_on_device(what, tensors):
+    for t, name in tensors:
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AdaispError(f"{what}: {name} must be a HIP device tensor (there is no CPU path)")
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise AdaispError(f"{what}: {name} must be a contiguous uint8 tensor, got {t.dtype}")
+    desc = tensors[-1][0]
+    if desc.numel() % UNPROCESS_DESC.itemsize:
+        raise AdaispError(f"{what}: desc holds {desc.numel()} bytes, not a whole number of {UNPROCESS_DESC.itemsize}-byte records")
+    return desc.numel() // UNPROCESS_DESC.itemsize
+
+
+def _pattern(pattern):
+    return CFA[pattern.upper()] if isinstance(pattern, str) else int(pattern)
+
+
+def unprocess_bayer(src, desc, S, seed=0, flags=0, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None):
+    """adaisp_unprocess_bayer: `unprocess` seen through a colour filter array and quantised -> uint16 [B,S,S] on the
+    device. src / desc / S / seed / flags as `unprocess`; a sample is the channel the CFA keeps at that pixel of the image
+    (phase from the image's origin), clamp(rint(v * (white - black)) + black, 0, 65535), and `black` outside the image."""
+    L = load()
+    B, S = _bytes_on_device("unprocess_bayer", ((src, "src"), (desc, "desc"))), int(S)
+    if out is None:
+        out = torch.empty((max(B, 1), max(S, 1), max(S, 1)), dtype=torch.uint16, device=src.device)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, S, S) or out.dtype not in (torch.uint16, torch.int16)
+          or not out.is_contiguous() or out.device != src.device):
+        raise AdaispError(f"unprocess_bayer: out must be a contiguous uint16 [{B},{S},{S}] tensor on {src.device}")
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_unprocess_bayer(src.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, int(seed) & (2 ** 64 - 1),
+                                      int(flags), _pattern(pattern), float(black_level), float(white_level), _stream())
+    _check(rc, "adaisp_unprocess_bayer")
+    _wrote(out)
+    return out
+
+
+def demosaic_rects(raw, desc, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None):
+    """adaisp_demosaic_rects: the letterboxed uint16 [B,S,S] plane of `unprocess_bayer` and its descriptors -> planar fp32
+    [B,3,S,S]: `demosaic` inside every image's own rectangle (phase and mirror at the rectangle), exactly 0 outside."""
+    L = load()
+    if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda":
+        raise AdaispError("demosaic_rects: raw must be a HIP device tensor (there is no CPU path)")
+    B = _bytes_on_device("demosaic_rects", ((desc, "desc"),))
+    if raw.dtype not in (torch.uint16, torch.int16) or raw.dim() != 3 or raw.shape[1] != raw.shape[2] or not raw.is_contiguous():
+        raise AdaispError(f"demosaic_rects: raw must be a contiguous uint16 [B,S,S] tensor, got {raw.dtype} {tuple(raw.shape)}")
+    if raw.shape[0] != B or raw.device != desc.device:
+        raise AdaispError(f"demosaic_rects: {raw.shape[0]} planes on {raw.device} but {B} descriptors on {desc.device}")
+    S = int(raw.shape[1])
+    if out is None:
+        out = torch.empty((B, 3, S, S), dtype=torch.float32, device=raw.device)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, 3, S, S) or out.dtype != torch.float32
+          or not out.is_contiguous() or out.device != raw.device):
+        raise AdaispError(f"demosaic_rects: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {raw.device}")
+    with torch.cuda.device(raw.device):
+        rc = L.adaisp_demosaic_rects(raw.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, _pattern(pattern),
+                                     float(black_level), float(white_level), _stream())
+    _check(rc, "adaisp_demosaic_rects")
     _wrote(out)
     return out
 

@@ -73,6 +73,15 @@ int adaisp_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pa
                    hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }
 
+int adaisp_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S, int pattern,
+                          float black_level, float white_level, void* stream) {
+    if (!raw || !desc || !out || B < 1 || S < 1) return ADAISP_EINVAL;
+    if (pattern < 0 || pattern > 3 || !(white_level > black_level)) return ADAISP_EINVAL;
+    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.z; as adaisp_unprocess_bayer
+    return launch_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level,
+                                 static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+}
+
 int adaisp_process(int op, const float* img, float* out, const float* params, int param_stride, int B, int H, int W,
                    unsigned flags, void* stream) {
     int rc = check_common(img, out, params, param_stride, B, H, W);

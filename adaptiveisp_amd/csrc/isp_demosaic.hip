@@ -71,7 +71,96 @@ __global__ __launch_bounds__(256) void k_demosaic(const unsigned short* __restri
     }
 }
 
+// The same rule inside every image's own rectangle of a letterboxed S x S frame (adaisp_demosaic_rects): the plane of
+// adaisp_unprocess_bayer holds image b at (top, left), h x w, and black around it. The CFA phase and the mirror belong to
+// the rectangle (iy = y - top, ix = x - left; -1 -> 1, h -> h - 2), so a border pixel never averages with the pad and an
+// odd top / left keeps the colours in place; every output outside the rectangle is exactly 0. The tile grid covers the
+// frame; the staging reads through the rectangle's mirror, so a tile's ring comes from inside the image whatever lies
+// beside it. A tile that misses the rectangle stages nothing and writes zeros. Cells are aligned to the frame: 8-byte
+// stores when S is even and `out` 8-byte aligned (VEC), one store per sample otherwise.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_demosaic_rects(const unsigned short* __restrict__ raw,
+                                                        const adaisp_unprocess_desc* __restrict__ desc,
+                                                        float* __restrict__ out, int S, int ry, int rx, float black,
+                                                        float inv_range) {
+    __shared__ float s[LH][LW + 2];
+    const int b = blockIdx.z, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const adaisp_unprocess_desc& d = desc[b];
+    const int h = d.h, w = d.w, top = d.top, left = d.left;
+    // as adaisp_unprocess_bayer: a placement that does not fit the frame is never read from; an image without a second
+    // row or column has nothing to mirror onto and comes out all zero
+    const bool fits = h >= 2 && w >= 2 && top >= 0 && left >= 0 && top <= S - h && left <= S - w;
+    const bool hit = fits && y0 < top + h && y0 + TH > top && x0 < left + w && x0 + TW > left;   // workgroup-uniform
+    const long plane = (long)S * S;
+    if (hit) {
+        const unsigned short* __restrict__ src = raw + (long)b * plane + (long)top * S + left;
+        for (int i = threadIdx.x; i < LH * LW; i += 256) {
+            const int ly = i / LW, lx = i - ly * LW;
+            const int y = mirror(y0 + ly - 1 - top, h), x = mirror(x0 + lx - 1 - left, w);
+            s[ly][lx] = ((float)src[(long)y * S + x] - black) * inv_range;
+        }
+        __syncthreads();
+    }
+    float* __restrict__ o = out + (long)b * 3 * plane;
+    const int cx = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int cy = (threadIdx.x >> 6) + 4 * k;
+        const int gx = x0 + 2 * cx, gy = y0 + 2 * cy;
+        if (gx >= S || gy >= S) continue;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            float r[2], g[2], bl[2];
+            const int iy = gy + dy - top;
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ix = gx + dx - left;
+                r[dx] = g[dx] = bl[dx] = 0.0f;
+                if (!hit || iy < 0 || iy >= h || ix < 0 || ix >= w) continue;
+                const int ly = 2 * cy + dy + 1, lx = 2 * cx + dx + 1;
+                const float c = s[ly][lx];
+                const float n = s[ly - 1][lx], so = s[ly + 1][lx], we = s[ly][lx - 1], e = s[ly][lx + 1];
+                const float cross = ((n + so) + (we + e)) * 0.25f;
+                const float diag = ((s[ly - 1][lx - 1] + s[ly - 1][lx + 1]) + (s[ly + 1][lx - 1] + s[ly + 1][lx + 1])) * 0.25f;
+                const float horiz = (we + e) * 0.5f, vert = (n + so) * 0.5f;
+                const int py = (iy - ry) & 1, px = (ix - rx) & 1;                // 0,0 = red site; 1,1 = blue site
+                if (py == 0 && px == 0) { r[dx] = c; g[dx] = cross; bl[dx] = diag; }
+                else if (py == 0) { r[dx] = horiz; g[dx] = c; bl[dx] = vert; }
+                else if (px == 0) { r[dx] = vert; g[dx] = c; bl[dx] = horiz; }
+                else { r[dx] = diag; g[dx] = cross; bl[dx] = c; }
+            }
+            if (gy + dy >= S) continue;                                          // odd S: the last cell row is half a cell
+            const long off = (long)(gy + dy) * S + gx;
+            if (VEC) {
+                *reinterpret_cast<float2*>(o + off) = make_float2(r[0], r[1]);
+                *reinterpret_cast<float2*>(o + plane + off) = make_float2(g[0], g[1]);
+                *reinterpret_cast<float2*>(o + 2 * plane + off) = make_float2(bl[0], bl[1]);
+            } else {
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx)
+                    if (gx + dx < S) {
+                        o[off + dx] = r[dx];
+                        o[plane + off + dx] = g[dx];
+                        o[2 * plane + off + dx] = bl[dx];
+                    }
+            }
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
+                                 int pattern, float black, float white, hipStream_t s) {
+    const int ry = pattern >> 1, rx = pattern & 1;
+    dim3 grid((S + TW - 1) / TW, (S + TH - 1) / TH, B);
+    const float inv = 1.0f / (white - black);
+    if (S % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0)
+        hipLaunchKernelGGL((k_demosaic_rects<true>), grid, dim3(256), 0, s, raw, desc, out, S, ry, rx, black, inv);
+    else
+        hipLaunchKernelGGL((k_demosaic_rects<false>), grid, dim3(256), 0, s, raw, desc, out, S, ry, rx, black, inv);
+    return hipGetLastError();
+}
 
 hipError_t launch_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black, float white,
                            hipStream_t s) {

@@ -81,6 +81,8 @@ hipError_t launch_pool64(const float* img, float* pooled, int B, int H, int W, h
 hipError_t launch_pool64_bwd(const float* grad_pooled, float* grad_img, int B, int H, int W, hipStream_t s);
 hipError_t launch_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black, float white,
                            hipStream_t s);
+hipError_t launch_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
+                                 int pattern, float black, float white, hipStream_t s);
 hipError_t launch_backward_params(const float* img, const float* grad_out, const int32_t* ids,
                                   const float* params, int pstride, float* grad_params,
                                   int B, int H, int W, unsigned flags, hipStream_t s);

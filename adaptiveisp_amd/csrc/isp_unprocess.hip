@@ -9,14 +9,13 @@
 //   ADAISP_UNP_NOISE:    x = clip(x + N(0, 1) sqrt(x shot + read))         add_read_and_shot_noise, :177-181
 //
 // The reference pads AFTER the conversion (letterbox of the unprocessed image, dataset.py:458-475), so the pad gets no
-// noise. The normals come from Philox4x32-10 (Salmon et al., SC'11) keyed by (seed, image serial) with the pixel's
-// index inside the un-padded image as the counter, then Box-Muller: an image's noise depends on (seed, serial) alone,
-// not on its batch, its place in it, its staging offset or the launch geometry.
+// noise. The chain's device functions and the noise generator live in isp_unprocess_math.h, shared with the Bayer sensor
+// (isp_sensor.hip).
 //
 // Mapping from the output side: a lane owns 4 consecutive samples of one output row and writes them to each plane as
 // one 16-byte store (S % 4 == 0 and a 16-byte aligned `out`; scalar stores otherwise). It reads the <= 12 source bytes
 // it needs with byte loads, so an image may start at any byte offset of `src`.
-#include "isp_internal.h"
+#include "isp_unprocess_math.h"
 
 static_assert(sizeof(adaisp_unprocess_desc) == 96, "adaisp_unprocess_desc is 96 bytes (adaptiveisp_amd/_lib.py)");
 
@@ -24,68 +23,6 @@ namespace adaisp {
 namespace {
 
 constexpr int UNP_THREADS = 256;   // = the 256 entries of the per-image tone table
-
-struct Philox4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ Philox4 philox4x32_10(Philox4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = Philox4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-// 24-bit uniforms are exact in fp32: u1 in (0, 1] (log never sees 0), u2 in [0, 1)
-__device__ __forceinline__ float unit_open0(uint32_t v) { return (float)((v >> 8) + 1u) * 0x1.0p-24f; }
-__device__ __forceinline__ float unit_closed0(uint32_t v) { return (float)(v >> 8) * 0x1.0p-24f; }
-
-// three N(0, 1) draws for pixel `idx` of image (seed, serial): Box-Muller on (x, y) gives two, on (z, w) one
-__device__ __forceinline__ void normals3(uint64_t seed, uint64_t serial, uint32_t idx, float n[3]) {
-    const Philox4 r = philox4x32_10(Philox4{idx, (uint32_t)(serial >> 32), (uint32_t)(seed >> 32), 0u},
-                                    (uint32_t)seed, (uint32_t)serial);
-    float s0, c0, s1, c1;
-    const float r0 = sqrtf(-2.0f * logf(unit_open0(r.x)));
-    sincospif(2.0f * unit_closed0(r.y), &s0, &c0);
-    const float r1 = sqrtf(-2.0f * logf(unit_open0(r.z)));
-    sincospif(2.0f * unit_closed0(r.w), &s1, &c1);
-    n[0] = r0 * c0;
-    n[1] = r0 * s0;
-    n[2] = r1 * c1;
-}
-
-__device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-
-// inverse_smoothstep then gamma_expansion (:53-61) of one 8-bit value at the image's pre-scale
-__device__ __forceinline__ float tone_gamma(int u8, float prescale) {
-    const float x = clip01((float)u8 / 255.0f * prescale);
-    return powf(fmaxf(0.5f - sinf(asinf(1.0f - 2.0f * x) / 3.0f), 1e-8f), 2.2f);
-}
-
-// the rest of the chain for one pixel: t = tone_gamma of R, G, B in, the output RGB out
-template <bool NOISE>
-__device__ __forceinline__ void unprocess_px(const float t[3], float v[3], const float* __restrict__ p, uint64_t seed,
-                                             uint64_t serial, uint32_t idx) {
-    float y[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)                                                      // apply_ccm, :63-68
-        y[c] = (t[0] * p[ADAISP_UNP_CCM + 3 * c] + t[1] * p[ADAISP_UNP_CCM + 3 * c + 1]) + t[2] * p[ADAISP_UNP_CCM + 3 * c + 2];
-    const float gray = ((y[0] + y[1]) + y[2]) / 3.0f;                                // safe_invert_gains, :70-80
-    const float m = fmaxf(gray - 0.9f, 0.0f) / 0.1f;
-    const float mask = m * m;
-    float n[3] = {0.0f, 0.0f, 0.0f};
-    if (NOISE) normals3(seed, serial, idx, n);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float g = p[ADAISP_UNP_GAIN + c];
-        float x = clip01(y[c] * fmaxf(mask + (1.0f - mask) * g, g)) * p[ADAISP_UNP_RATIO];
-        if (NOISE) x = clip01(x + n[c] * sqrtf(x * p[ADAISP_UNP_SHOT] + p[ADAISP_UNP_READ]));
-        v[c] = x;
-    }
-}
 
 template <int MODE, bool VEC>   // MODE: 0 convert, 1 unprocess, 2 unprocess + noise
 __global__ __launch_bounds__(UNP_THREADS) void k_unprocess(const uint8_t* __restrict__ src,

@@ -10,6 +10,11 @@ of the reference's fp32 / fp64), and one adaisp_unprocess launch per batch conve
 letterboxes on the device. The random draws of the metadata are the reference's, in its order
 (`sample_unprocess_params`); the per-sample normals come from a counter-based generator on the device, so the noise is
 equal to the reference's in distribution, not in value.
+
+sensor="bayer" puts a simulated camera between the two: adaisp_unprocess_bayer keeps the one colour a Bayer filter passes
+at every pixel of the unprocessed (and, with add_noise, noisy) image and quantises it to a raw_bits plane, and
+adaisp_demosaic_rects interpolates the batch back from that plane, so the noise the policy sees is the demosaiced noise
+of a raw sensor rather than white noise per channel (the reference's `unprocess` + `mosaic`, isp/unprocess_np.py:217-245).
 """
 import random
 from collections import deque
@@ -102,15 +107,39 @@ class ImageFolderSource:
     device scratch that adaisp_unprocess then reads. Same bytes as the host path (the kernel reproduces val/loader.py's
     arithmetic), same metadata draws and noise keys. HIP devices only.
 
+    sensor="bayer" (either data_name, with or without noise, either resize): the same descriptors drive
+    adaisp_unprocess_bayer into a reused uint16 device plane (colour filter `cfa`, white level 2**raw_bits - 1,
+    `black_level`, default 2**(raw_bits - 6), 0 below 6 bits) and adaisp_demosaic_rects out of it; the batch keeps its
+    [n,3,S,S] fp32 shape, in [0, 1] over the black..white range. Metadata draws, serials and noise keys are those of
+    sensor="rgb": the same seed gives the same sensor parameters in both modes. HIP devices only; an image with a side
+    under 2 pixels has no Bayer cell and raises ValueError.
+
     On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` has no CPU path and raises."""
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
-                 use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host"):
+                 use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host", sensor="rgb", cfa="RGGB", raw_bits=12,
+                 black_level=None):
+        from ._lib import CFA
         if data_name not in ("lod", "coco"):
             raise ValueError(f"data_name must be 'lod' or 'coco', got {data_name!r}")
         if resize not in ("host", "device"):
             raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
+        if sensor not in ("rgb", "bayer"):
+            raise ValueError(f"sensor must be 'rgb' or 'bayer', got {sensor!r}")
+        if not isinstance(cfa, str) or cfa.upper() not in CFA:
+            raise ValueError(f"cfa must be one of {sorted(CFA)}, got {cfa!r}")
+        if isinstance(raw_bits, bool) or not isinstance(raw_bits, (int, np.integer)) or not 1 <= raw_bits <= 16:
+            raise ValueError(f"raw_bits must be an integer in [1, 16], got {raw_bits!r}")
+        self.sensor, self.cfa, self.raw_bits = sensor, cfa.upper(), int(raw_bits)
+        self.white_level = 2 ** self.raw_bits - 1
+        self.black_level = (2 ** (self.raw_bits - 6) if self.raw_bits >= 6 else 0) if black_level is None else black_level
+        if not 0 <= self.black_level < self.white_level or int(self.black_level) != self.black_level:
+            raise ValueError(f"black_level must be a whole number in [0, {self.white_level}), got {black_level!r}")
+        self.black_level = int(self.black_level)
         self.device = torch.device(device)
+        if sensor == "bayer" and self.device.type != "cuda":
+            raise RuntimeError("ImageFolderSource(sensor='bayer'): the sensor and its demosaic run on the HIP device only "
+                               "(adaisp_unprocess_bayer, adaisp_demosaic_rects); there is no CPU path")
         if data_name == "coco" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(data_name='coco'): the unprocess runs on the HIP device only "
                                "(adaisp_unprocess); there is no CPU path")
@@ -139,6 +168,7 @@ class ImageFolderSource:
         self._slots = [dict(host=None, event=None) for _ in range(2)]
         self._slot = 0
         self._dev = None
+        self._plane = None                        # sensor="bayer": the uint16 plane between the two kernels
 
     def __len__(self):
         return len(self.files)
@@ -150,7 +180,8 @@ class ImageFolderSource:
 
     def describe(self):
         kind = "coco (unprocess" + (", noise" if self.add_noise else "") + ")" if self.data_name == "coco" else "lod"
-        return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "")
+        bayer = f", bayer {self.cfa} {self.raw_bits}-bit black {self.black_level}" if self.sensor == "bayer" else ""
+        return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "") + bayer
 
     # ------------------------------------------------------------------------------------------------------ order
     def _next_index(self):
@@ -257,6 +288,8 @@ class ImageFolderSource:
                 final.append((im.shape[0], im.shape[1], off))
                 off += im.size
         for b, ((h, w, src_offset), (im, top, left, *_rest)) in enumerate(zip(final, items)):
+            if self.sensor == "bayer" and min(h, w) < 2:
+                raise ValueError(f"{items[b][4]}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
             desc[b]["src_offset"], desc[b]["h"], desc[b]["w"] = src_offset, h, w
             desc[b]["top"], desc[b]["left"], desc[b]["serial"] = top, left, self.serial
             self.serial += 1
@@ -292,7 +325,14 @@ class ImageFolderSource:
             slot["event"].record()
             if lay is not None:
                 self._resize_on_device(lay, total)
-            return _lib.unprocess(self._dev[base:need], self._dev[:B * desc.itemsize], S, seed=self.seed, flags=flags)
+            pixels, records = self._dev[base:need], self._dev[:B * desc.itemsize]
+            if self.sensor != "bayer":
+                return _lib.unprocess(pixels, records, S, seed=self.seed, flags=flags)
+            if self._plane is None or self._plane.shape[0] < B:
+                self._plane = torch.empty((B, S, S), dtype=torch.uint16, device=self.device)
+            levels = dict(pattern=self.cfa, black_level=self.black_level, white_level=self.white_level)
+            raw = _lib.unprocess_bayer(pixels, records, S, seed=self.seed, flags=flags, out=self._plane[:B], **levels)
+            return _lib.demosaic_rects(raw, records, **levels)
 
     def _resize_on_device(self, lay, total):
         """The two adaisp_resize_u8 calls of a staged batch (see _resize_plan), on the current stream."""

@@ -176,6 +176,36 @@ int adaisp_unprocess(const uint8_t* src, const adaisp_unprocess_desc* desc, floa
                      uint64_t seed, unsigned flags, void* stream);
 
 /*
+ * Simulated Bayer sensor: adaisp_unprocess through a colour filter array and a quantiser, the half of the reference's
+ * `unprocess` that adaisp_unprocess leaves out (`mosaic`, isp/unprocess_np.py:217-245, :82-98). src, desc, B, S, seed
+ * and flags are adaisp_unprocess's. out: uint16 [B,S,S]. Inside an image's rectangle, pixel (iy, ix) in the IMAGE's
+ * coordinates keeps the one channel c that `pattern` (ADAISP_CFA_*) assigns to it (the phase belongs to the image, not to
+ * the frame), and stores
+ *     clamp(rintf(v * (white_level - black_level)) + black_level, 0, 65535)
+ * where v is exactly the fp32 value adaisp_unprocess writes for channel c of that pixel under the same flags,
+ * parameters, seed and serial; with ADAISP_UNP_NOISE it carries the c-th of the pixel's three normals. Every sample
+ * outside the rectangle is black_level; a placement that does not fit the frame gives an all-black image. The levels are
+ * meant to be whole numbers (the conversion to uint16 drops a fraction). ADAISP_EINVAL: null pointers, bad flags,
+ * unknown pattern, white_level <= black_level; ADAISP_ESHAPE: B > 65535 or S > 32768. No allocation, no host
+ * synchronisation: capturable in a hipGraph.
+ */
+int adaisp_unprocess_bayer(const uint8_t* src, const adaisp_unprocess_desc* desc, uint16_t* out, int B, int S,
+                           uint64_t seed, unsigned flags, int pattern, float black_level, float white_level,
+                           void* stream);
+
+/*
+ * adaisp_demosaic's bilinear rule inside every image's own rectangle of a letterboxed plane (the output of
+ * adaisp_unprocess_bayer, with the same descriptors): raw uint16 [B,S,S] -> planar fp32 [B,3,S,S]. The CFA phase is
+ * relative to the rectangle's origin and the mirror (-1 -> 1, h -> h - 2) is taken at the rectangle's edges, so border
+ * pixels never average with the pad and an odd top / left keeps the colours in place: inside the rectangle the output is
+ * adaisp_demosaic of the crop, bit for bit (h and w may be odd: the crop continued by its mirror). Every output outside
+ * the rectangle is exactly 0; an image with h < 2 or w < 2, or whose placement does not fit the frame, comes out all
+ * zero. Any S >= 1. Errors and limits as adaisp_unprocess_bayer. Capturable.
+ */
+int adaisp_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S, int pattern,
+                          float black_level, float white_level, void* stream);
+
+/*
  * Replay-pool resampling on the device: the pixel work of `load_image` (dataloaders.py:735-750: longer side to S, area
  * filter when shrinking, bilinear otherwise) and of `letterbox`'s resize to the un-padded size (augmentations.py:111-141),
  * uint8 HWC BGR -> uint8 HWC BGR, every image with its own sizes, mode and byte offsets. Each mode reproduces the
