@@ -1,6 +1,7 @@
 // C-ABI of libadayolo.so (include/adayolo.h): argument checks + launches. No allocation, no sync.
 #include "yolo_internal.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -112,9 +113,30 @@ static bool bad_frame(int B, int H, int W, int Hp, int pad_top) {
     return B <= 0 || H <= 0 || W <= 0 || Hp < H || pad_top < 0 || pad_top + H > Hp;
 }
 
+// ---- MFMA shape per ring-kernel family (yolo_internal.h). Built-in defaults: what profiles/mfma_shape_ab.txt measured faster.
+static int shape_default(ShapeFamily f) {
+    const char* e = getenv(f == kShapePp ? "ADAYOLO_MFMA_SHAPE_PP" : "ADAYOLO_MFMA_SHAPE_PP128");
+    const int v = e ? atoi(e) : 0;
+    if (v == 16 || v == 32) return v;
+    return f == kShapePp ? ADAYOLO_MFMA_SHAPE_PP_DEFAULT : ADAYOLO_MFMA_SHAPE_PP128_DEFAULT;
+}
+static std::atomic<int> g_mfma_shape[2] = {{shape_default(kShapePp)}, {shape_default(kShapePp128)}};
+int adayolo::mfma_shape(ShapeFamily f) { return g_mfma_shape[f].load(std::memory_order_relaxed); }
+
 extern "C" {
 
 int adayolo_abi_version(void) { return ADAYOLO_ABI_VERSION; }
+
+int adayolo_set_mfma_shape(int family, int shape) {
+    if ((family != 0 && family != 1) || (shape != 16 && shape != 32)) return ADAYOLO_EINVAL;
+    g_mfma_shape[family].store(shape, std::memory_order_relaxed);
+    return ADAYOLO_OK;
+}
+
+int adayolo_get_mfma_shape(int family) {
+    if (family != 0 && family != 1) return ADAYOLO_EINVAL;
+    return mfma_shape(static_cast<ShapeFamily>(family));
+}
 
 const char* adayolo_strerror(int code) {
     switch (code) {

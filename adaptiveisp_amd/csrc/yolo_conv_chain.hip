@@ -31,6 +31,8 @@ __device__ unsigned long long g_chain_acc[16];
 // Dependencies: a tile waits for the m-tiles of the producing layer its input window and its residual rows lie in (arrival
 // counters, bumped when a tile's written-through stores are complete). It only ever waits for items that come before it in
 // the hand-out order, and those are held by workgroups that are running: no deadlock whatever number of workgroups is resident.
+// MSPP / MS128: the MFMA shape of the 256 x 256 / 256 x 128 tile bodies (32 or 16: yolo_conv_pp.hip)
+template <int MSPP, int MS128>
 __global__ __launch_bounds__(512) void k_conv_chain(const ChainArgs c) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -115,9 +117,9 @@ __global__ __launch_bounds__(512) void k_conv_chain(const ChainArgs c) {
 #ifdef ADAYOLO_CHAIN_STAMPS
         PP_STAMP(10);                                        // loop top: item record, slow path, layer arguments
 #endif
-        if (a.chain_tile == 1) pp128c::conv_tile<0, false, true>(a, hd[1], smem, cx);
-        else if (a.w2) ppc::conv_tile<0, true, true>(a, hd[1], smem, cx);
-        else ppc::conv_tile<0, false, true>(a, hd[1], smem, cx);
+        if (a.chain_tile == 1) pp128c::conv_tile<0, false, true, MS128>(a, hd[1], smem, cx);
+        else if (a.w2) ppc::conv_tile<0, true, true, MSPP>(a, hd[1], smem, cx);
+        else ppc::conv_tile<0, false, true, MSPP>(a, hd[1], smem, cx);
         cx.pending = hd[2];
         item = __builtin_amdgcn_readfirstlane(sched[0]);
         ready = __builtin_amdgcn_readfirstlane(sched[1]);
@@ -165,14 +167,17 @@ __global__ __launch_bounds__(512) void k_conv_chain(const ChainArgs c) {
 
 static hipError_t launch_chain(const ChainArgs& c, int grid, hipStream_t s) {
     static_assert(kSmemChain <= 160 * 1024, "LDS budget");
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_chain), hipFuncAttributeMaxDynamicSharedMemorySize,
+    // each tile type on its family's shape, read when the launch enqueues
+    const int mspp = mfma_shape(kShapePp), ms128 = mfma_shape(kShapePp128), which = (mspp == 16 ? 1 : 0) + (ms128 == 16 ? 2 : 0);
+    void (*const kerns[4])(const ChainArgs) = {k_conv_chain<32, 32>, k_conv_chain<16, 32>, k_conv_chain<32, 16>, k_conv_chain<16, 16>};
+    static bool configured[4] = {false, false, false, false};
+    if (!configured[which]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[which]), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            kSmemChain);
         if (e != hipSuccess) return e;
-        configured = true;
+        configured[which] = true;
     }
-    hipLaunchKernelGGL(k_conv_chain, dim3(grid), dim3(512), kSmemChain, s, c);
+    hipLaunchKernelGGL(kerns[which], dim3(grid), dim3(512), kSmemChain, s, c);
     return hipGetLastError();
 }
 

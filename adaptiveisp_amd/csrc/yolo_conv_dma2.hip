@@ -8,7 +8,10 @@
 //     swizzled k-chunk) is folded once into a per-row base pointer and a 9-bit tap-validity mask; a k-step
 //     adds one wave-uniform offset and selects the zero block with two v_cndmask — ~6 VALU per DMA
 //     instead of ~20, no branches;
-//   * v_mfma_f32_32x32x16_bf16: half the MFMA instructions for the same flops and the same LDS traffic;
+//   * v_mfma_f32_32x32x16_bf16: half the MFMA instructions of 16x16x32 for the same flops and the same LDS traffic — which
+//     does not decide which is faster: the chip holds a different clock on the two shapes. Measured in the ring kernels that
+//     grew out of this one (yolo_conv_pp.hip / yolo_conv_pp128.hip build both; profiles/mfma_shape_ab.txt): 16x16x32 is
+//     1.8 % faster on the pipelined step. This kernel was not compared;
 //     with the (row>>1)&7 XOR key the 32-row fragment reads are bank-conflict-free.
 #include "yolo_device.h"
 #include <type_traits>

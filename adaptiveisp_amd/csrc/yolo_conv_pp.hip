@@ -20,6 +20,11 @@
 //     in flight) — never vmcnt(0). A wait in phase X's MFMA section retires data that is first read in phase X+2's
 //     load section (with the stagger, only then has every wave passed a barrier behind every other wave's wait).
 //
+//   * MS: the MFMA shape of the k-loop. 32 = v_mfma_f32_32x32x16_bf16 as described above; 16 = v_mfma_f32_16x16x32_bf16 on
+//     the same wave tile, ring, DMA schedule, barriers and waits: a phase is 16 MFMAs (four 16 px x two 16 ch fragments x two
+//     K = 32 steps) of ~16 cycles on 8 + 4 ds_read_b128, the accumulators are f32x4 acc[4][8]. The chip can hold a different
+//     clock on the two shapes, so both are built and the faster by wall time is the default (adayolo_set_mfma_shape).
+//
 // Restrictions (the launcher falls back otherwise): Cin % 64 == 0, Cout % 256 == 0.
 // Measured and dropped (round 2): channel chunk outer / tap inner k order, so that consecutive k-tiles ask for almost the same
 // activation lines (L1 hits instead of L2 fetches): 3-4 % SLOWER on every layer; a non-temporal / system-scope cache policy on
@@ -89,7 +94,7 @@ struct KPos {
 // the unfused kernel would read back from memory.
 // One 256 x 256 tile. CHAIN: `lid` is handed in, output stores are written through (sc1) and this workgroup's previous tile is
 // published once they are known complete; wave 0 fetches the next item and checks its inputs in the shadow of the epilogue.
-template <int ABL, bool FUSE, bool CHAIN>
+template <int ABL, bool FUSE, bool CHAIN, int MS = 32>
 __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsigned char* smem, ChainCtx& cx) {
     float* bias_s = reinterpret_cast<float*>(smem + (kEpi > 2 * kBuf ? kEpi : 2 * kBuf));
     PP_STAMP(0);
@@ -204,21 +209,32 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
     auto stage_a = [&](int h, unsigned char* buf, const KPos& p, bool live) { stage_a1(h, 0, buf, p, live); stage_a1(h, 1, buf, p, live); };
     auto stage_w = [&](int h, unsigned char* buf, const KPos& p, bool live) { stage_w1(h, 0, buf, p, live); stage_w1(h, 1, buf, p, live); };
 
+    static_assert(MS == 32 || MS == 16, "MFMA shape: 32x32x16 or 16x16x32");
     f32x16 acc[2][4];                                   // [channel frag][pixel frag]
+    f32x4 acc16[4][8];                                  // MS 16: [16-channel frag][16-pixel frag]; the same 128 registers
+    if constexpr (MS == 32) {
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[ni][mi][e] = 0.0f;
+    } else {
+#pragma unroll
+        for (int cf = 0; cf < 4; ++cf)
+#pragma unroll
+            for (int pf = 0; pf < 8; ++pf) acc16[cf][pf] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
 
     // fragment addressing (32x32x16): lane -> tile row (lane & 31), 16-byte k-chunk 2*kk + (lane >> 5), XOR key
     // (row >> 1) & 7 — the same for every fragment of this lane because fragment origins are multiples of 32 rows
-    const int frow = lane & 31, fq = lane >> 5, key = (frow >> 1) & 7;
+    // (16x16x32): tile row (lane & 15), 16-byte k-chunk 4*k2 + (lane >> 4), the same key rule — fragment origins are
+    // multiples of 16 rows; the 16 lanes of a row group read 16 distinct bank quads
+    const int frow = MS == 32 ? lane & 31 : lane & 15, fq = MS == 32 ? lane >> 5 : lane >> 4, key = (frow >> 1) & 7;
     const int abase = (wm * 128 + frow) * kRow, wbase = kTile + (wn * 64 + frow) * kRow;
     int koff[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) koff[kk] = ((2 * kk + fq) ^ key) << 4;
+    for (int kk = 0; kk < 4; ++kk) koff[kk] = MS == 32 ? ((2 * kk + fq) ^ key) << 4 : ((4 * (kk & 1) + fq) ^ key) << 4;
 
     PP_STAMP(1);
     // ---- prologue: bias (one 1 KB DMA by wave 0), k-tile 0 complete, W0 / A0 of k-tile 1 (what P3 / P4 of the
@@ -250,6 +266,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
         barrier();
     }
 
+    // MS 16: af[pf >> 1][2 * (pf & 1) + k2] is the 16-pixel fragment pf of the half at k-step k2, w[2 * cf + k2] the 16-channel
+    // fragment cf — the same 8 + 4 reads of the same 64 / 32 rows
     bf16x8 af[2][4], wx[4], wy[4];
     auto read_a = [&](const unsigned char* buf, int half) {
         if (ABL == 2) return;
@@ -257,13 +275,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
-                af[mi][kk] = *reinterpret_cast<const bf16x8*>(buf + abase + (2 * half + mi) * 32 * kRow + koff[kk]);
+                af[mi][kk] = MS == 32 ? *reinterpret_cast<const bf16x8*>(buf + abase + (2 * half + mi) * 32 * kRow + koff[kk])
+                                      : *reinterpret_cast<const bf16x8*>(buf + abase + (4 * half + 2 * mi + (kk >> 1)) * 16 * kRow + koff[kk]);
     };
     auto read_w = [&](const unsigned char* buf, int half, bf16x8 (&w)[4]) {
         if (ABL == 2) return;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
-            w[kk] = *reinterpret_cast<const bf16x8*>(buf + wbase + half * 32 * kRow + koff[kk]);
+            w[kk] = MS == 32 ? *reinterpret_cast<const bf16x8*>(buf + wbase + half * 32 * kRow + koff[kk])
+                             : *reinterpret_cast<const bf16x8*>(buf + wbase + (2 * half + (kk >> 1)) * 16 * kRow + koff[kk]);
     };
     // MFMA section of one phase: 8 MFMAs with the phase's two LDS-DMA pieces issued in their shadow, then the counted
     // wait that retires the half-tile issued three phases ago (readable from the load section two phases on)
@@ -272,6 +292,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
 #if PP_PRIO_MODE == 0
         __builtin_amdgcn_s_setprio(1);
 #endif
+        if constexpr (MS == 32) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
@@ -285,6 +306,26 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
+        }
+        } else {
+            // 16 MFMAs of half the cycles: k-step outer, so that every accumulator takes its two steps in ascending order
+            // eight MFMAs apart; the DMA pieces sit at the same points of the section (behind the 2nd and the 8th)
+#pragma unroll
+            for (int k2 = 0; k2 < 2; ++k2)
+#pragma unroll
+                for (int cf = 0; cf < 2; ++cf)
+#pragma unroll
+                    for (int pf = 0; pf < 4; ++pf) {
+                        if (ABL != 2)
+                            acc16[2 * ni + cf][4 * half + pf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                w[2 * cf + k2], af[pf >> 1][2 * (pf & 1) + k2], acc16[2 * ni + cf][4 * half + pf], 0, 0, 0);
+                        const int n = 8 * k2 + 4 * cf + pf;
+                        if (n == 1 || n == 7) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (ABL != 5) dma16(n == 1 ? g0 : g1, n == 1 ? d0 : d1);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
         }
 #if PP_PRIO_MODE == 0
         __builtin_amdgcn_s_setprio(0);
@@ -346,10 +387,17 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
     barrier();
 
     if (ABL == 6) {                                      // measurement build: prologue + k-loop only
+        if constexpr (MS == 32) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi) asm volatile("" ::"v"(acc[ni][mi]));
+        } else {
+#pragma unroll
+            for (int cf = 0; cf < 4; ++cf)
+#pragma unroll
+                for (int pf = 0; pf < 8; ++pf) asm volatile("" ::"v"(acc16[cf][pf]));
+        }
         return;
     }
     // ---- epilogue. D[row = channel][col = pixel]: lane holds pixel (lane & 31) and channels 8*qd + 4*(lane >> 5) + (0..3)
@@ -358,6 +406,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
     //      as soon as its own fragment is converted — and writes whole 128-byte row segments (8 lanes x 16 B).
     //      (Storing 8/16-byte pieces straight from the fragment layout was measured 2x slower: 32 rows x 32 B per
     //      instruction instead of 8 rows x 128 B.)
+    //      MS 16: D is col = lane & 15 (pixel), row = 4 * (lane >> 4) + reg (channel): the four registers of a 16x16 fragment
+    //      are one 8-byte write at pixel row 16 pb + (lane & 15), channel 16 cb + 4 * (lane >> 4) (16 rows x 4 column groups per
+    //      instruction at pitch 144 B: conflict-free); the read side and everything behind it are the same.
     unsigned char* my = smem + wave * (128 * kEpiPitch);
     // CHAIN: the tile's outputs leave as 16-byte WRITE-THROUGH (sc1) buffer stores — complete, for every other CU and XCD, once
     // the storing wave's vmcnt reaches 0 (no release fence, i.e. no whole-L2 write-back); byte offsets are 32-bit (the caller
@@ -373,18 +424,19 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
     // are issued back to back (one wait each), not read -> wait -> load -> wait -> store four times over.
     auto epilogue = [&](auto silu_tag, auto res_tag) {
         constexpr bool kSilu = decltype(silu_tag)::value, kRes = decltype(res_tag)::value;
-        float4 bq[2][4];
+        float4 bq[2][4];                                         // MS 16: bq[0][cb]
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd)
-                bq[ni][qd] = *reinterpret_cast<const float4*>(bias_s + wn * 64 + ni * 32 + 8 * qd + 4 * (lane >> 5));
+                if (MS == 32) bq[ni][qd] = *reinterpret_cast<const float4*>(bias_s + wn * 64 + ni * 32 + 8 * qd + 4 * (lane >> 5));
+                else if (ni == 0) bq[0][qd] = *reinterpret_cast<const float4*>(bias_s + wn * 64 + 16 * qd + 4 * (lane >> 4));
         const int chunk = lane & 7, r0 = lane >> 3;
         const int mrow = m0 + wm * 128 + r0, n = n0 + wn * 64 + chunk * 8;
         unsigned short* const op = a.out + (long)mrow * a.out_cs + n;
         const unsigned short* const rp = kRes ? a.res + (long)mrow * a.res_cs + n : nullptr;
         const long ostep = 8L * a.out_cs, rstep = kRes ? 8L * a.res_cs : 0;
-        unsigned char* const wr = my + (lane & 31) * kEpiPitch + 8 * (lane >> 5);
+        unsigned char* const wr = MS == 32 ? my + (lane & 31) * kEpiPitch + 8 * (lane >> 5) : my + (lane & 15) * kEpiPitch + 8 * (lane >> 4);
         const unsigned char* const rd = my + r0 * kEpiPitch + chunk * 16;
         // (With a residual this epilogue is 14.9k cycles instead of 6.4k: the 128 KB residual tile arrives cold from HBM at the
         // per-CU streaming rate. Measured and dropped: requesting the rows 2 or 4 groups ahead instead of one — no change, the
@@ -410,9 +462,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int lid, unsi
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
                     unsigned lo, hi;
+                    if constexpr (MS == 32) {
                     bias_act_pack4<kSilu>(acc[ni][mi][4 * qd], acc[ni][mi][4 * qd + 1], acc[ni][mi][4 * qd + 2], acc[ni][mi][4 * qd + 3],
                                           bq[ni][qd], lo, hi);
                     *reinterpret_cast<u32x2*>(wr + mi * 32 * kEpiPitch + (ni * 32 + 8 * qd) * 2) = u32x2{lo, hi};
+                    } else {                                     // ni: the 16-pixel fragment of the group, qd: the 16-channel fragment
+                        const f32x4 d = acc16[qd][2 * mi + ni];
+                        bias_act_pack4<kSilu>(d[0], d[1], d[2], d[3], bq[0][qd], lo, hi);
+                        *reinterpret_cast<u32x2*>(wr + (2 * mi + ni) * 16 * kEpiPitch + 16 * qd * 2) = u32x2{lo, hi};
+                    }
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave wrote and reads: in-order LDS, no barrier
 #pragma unroll
@@ -546,11 +604,19 @@ __global__ __launch_bounds__(512) void k_conv_pp(const ConvArgs a) {
     conv_tile<ABL, FUSE, false>(a, xcd_remap(blockIdx.x, a.mtiles * a.ntiles), smem, none);
 }
 
+// the same kernel with the k-loop on v_mfma_f32_16x16x32_bf16 (MS 16)
+template <int ABL, bool FUSE>
+__global__ __launch_bounds__(512) void k_conv_pp_m16(const ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ChainCtx none{nullptr, -1};
+    conv_tile<ABL, FUSE, false, 16>(a, xcd_remap(blockIdx.x, a.mtiles * a.ntiles), smem, none);
+}
+
 #ifndef ADAYOLO_TILE_ONLY
-template <int ABL, bool FUSE = false>
+template <int ABL, bool FUSE = false, int MS = 32>
 static hipError_t launch(ConvArgs a, hipStream_t s) {
     static_assert(kSmem <= 160 * 1024, "LDS budget");
-    auto kern = k_conv_pp<ABL, FUSE>;
+    auto kern = MS == 16 ? k_conv_pp_m16<ABL, FUSE> : k_conv_pp<ABL, FUSE>;
     static bool configured = false;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -574,7 +640,12 @@ static hipError_t launch(ConvArgs a, hipStream_t s) {
 // the shape is not served (the caller falls back to the default kernel).
 hipError_t launch_conv_pp(ConvArgs a, hipStream_t s, int variant) {
     if (a.Cin % 64 || a.Cout % 256) return hipErrorInvalidValue;
+    const bool m16 = mfma_shape(kShapePp) == 16;         // read at enqueue time: a captured graph keeps what it captured
 #ifdef ADAYOLO_MEASURE
+    if (m16) {
+        if (variant == 56) return pp::launch<6, false, 16>(a, s);
+        if (variant == 57) return pp::launch<7, false, 16>(a, s);
+    }
     if (variant == 51) return pp::launch<1>(a, s);
     if (variant == 52) return pp::launch<2>(a, s);
     if (variant == 53) return pp::launch<3>(a, s);
@@ -589,11 +660,11 @@ hipError_t launch_conv_pp(ConvArgs a, hipStream_t s, int variant) {
     if (a.w2) {                                          // fused 1x1 second layer: the tile must hold all channels
         if (a.Cout != 256 || !a.bias2 || !a.out2) return hipErrorInvalidValue;
 #ifdef ADAYOLO_MEASURE
-        if (getenv("ADAYOLO_PP_STAMPS")) return pp::launch<7, true>(a, s);
+        if (getenv("ADAYOLO_PP_STAMPS")) return m16 ? pp::launch<7, true, 16>(a, s) : pp::launch<7, true>(a, s);
 #endif
-        return pp::launch<0, true>(a, s);
+        return m16 ? pp::launch<0, true, 16>(a, s) : pp::launch<0, true>(a, s);
     }
-    return pp::launch<0>(a, s);
+    return m16 ? pp::launch<0, false, 16>(a, s) : pp::launch<0>(a, s);
 }
 
 #ifdef ADAYOLO_MEASURE

@@ -18,6 +18,11 @@
 //     i.e. everything issued three phases ago is retired, and is first read two phases later (the distance the
 //     stagger needs): issue -> read = 5 phases. A slot is re-staged at least one phase after its last read.
 //
+//   * MS (see yolo_conv_pp.hip): 32 = v_mfma_f32_32x32x16_bf16 as above; 16 = v_mfma_f32_16x16x32_bf16 on the same wave
+//     tile and schedule — 16 MFMAs per phase (four 16 px x two 16 ch fragments x two K = 32 steps), f32x4 acc[4][4], the DMA
+//     pieces behind the 2nd, 6th, 10th and 14th MFMA. The split-K partials are stored in the shape's own lane order: writer
+//     and reducer of a launch are the same instantiation.
+//
 // Restrictions (the launcher falls back otherwise): Cin % 64 == 0, Cout % 128 == 0.
 // Measured and dropped (round 2, same outputs bit for bit): ONE phase per k-tile — all 16 fragments in one load section, 16
 // MFMAs per section, two barriers per k-tile instead of four, 190 registers — 71 vs 70 us on 512 -> 1024 @ 8x23x40; the same
@@ -64,7 +69,7 @@ struct KPos {                                 // wave-uniform position of a k-ti
 // (2-4 us better than tile-fastest).
 // CHAIN (yolo_chain.h): the tile is a work item of the persistent chain kernel — `gid` is handed in, the outputs leave as
 // written-through stores, the previous tile of the workgroup is published behind the prologue, wave 0 looks ahead.
-template <int ABL, bool SPLIT, bool CHAIN>
+template <int ABL, bool SPLIT, bool CHAIN, int MS = 32>
 __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsigned char* smem, ChainCtx& cx) {
     static_assert(!(SPLIT && CHAIN), "the chain runs whole tiles");
     float* bias_s = reinterpret_cast<float*>(smem + kRing);
@@ -181,33 +186,47 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
         barrier();
     }
 
+    static_assert(MS == 32 || MS == 16, "MFMA shape: 32x32x16 or 16x16x32");
     f32x16 acc[2][2];                                    // [channel frag][pixel frag]
+    f32x4 acc16[4][4];                                   // MS 16: [16-channel frag][16-pixel frag]; the same 64 registers
+    if constexpr (MS == 32) {
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[ni][mi][e] = 0.0f;
+    } else {
+#pragma unroll
+        for (int cf = 0; cf < 4; ++cf)
+#pragma unroll
+            for (int pf = 0; pf < 4; ++pf) acc16[cf][pf] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
 
     // fragment addressing (32x32x16): lane -> tile row (lane & 31), 16-byte k-chunk 2*kk + (lane >> 5), XOR key
-    const int frow = lane & 31, fq = lane >> 5, key = (frow >> 1) & 7;
+    // (16x16x32): tile row (lane & 15), k-chunk 4*k2 + (lane >> 4), the same key rule (fragment origins: multiples of 16 rows)
+    const int frow = MS == 32 ? lane & 31 : lane & 15, fq = MS == 32 ? lane >> 5 : lane >> 4, key = (frow >> 1) & 7;
     const int abase = (wm * 64 + frow) * kRow, wbase = kATile + (wn * 64 + frow) * kRow;
     int koff[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) koff[kk] = ((2 * kk + fq) ^ key) << 4;
+    for (int kk = 0; kk < 4; ++kk) koff[kk] = MS == 32 ? ((2 * kk + fq) ^ key) << 4 : ((4 * (kk & 1) + fq) ^ key) << 4;
 
+    // MS 16: af[pf >> 1][2 * (pf & 1) + k2] is the 16-pixel fragment pf at k-step k2, w[2 * cf + k2] the 16-channel fragment cf
+    // of the phase's half — the same 8 + 4 (+ 4) reads of the same rows
     bf16x8 af[2][4], wx[4], wy[4], wz[4];
     auto read_a = [&](const unsigned char* buf) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
-                af[mi][kk] = *reinterpret_cast<const bf16x8*>(buf + abase + mi * 32 * kRow + koff[kk]);
+                af[mi][kk] = MS == 32 ? *reinterpret_cast<const bf16x8*>(buf + abase + mi * 32 * kRow + koff[kk])
+                                      : *reinterpret_cast<const bf16x8*>(buf + abase + (2 * mi + (kk >> 1)) * 16 * kRow + koff[kk]);
     };
     auto read_w = [&](const unsigned char* buf, int ni, bf16x8 (&w)[4]) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
-            w[kk] = *reinterpret_cast<const bf16x8*>(buf + wbase + ni * 32 * kRow + koff[kk]);
+            w[kk] = MS == 32 ? *reinterpret_cast<const bf16x8*>(buf + wbase + ni * 32 * kRow + koff[kk])
+                             : *reinterpret_cast<const bf16x8*>(buf + wbase + (2 * ni + (kk >> 1)) * 16 * kRow + koff[kk]);
     };
     // MFMA section: 8 MFMAs, the phase's DMA instructions issued behind the 1st, 3rd, 5th and 7th, then the counted wait
     // source addresses are computed in the load section in front (see yolo_conv_pp.hip): between two MFMAs only
@@ -216,6 +235,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
 #if PP_PRIO_MODE == 0
         __builtin_amdgcn_s_setprio(1);
 #endif
+        if constexpr (MS == 32) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -228,6 +248,25 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
+        } else {
+            // k-step outer: every accumulator takes its two steps in ascending order, eight MFMAs apart; the DMA pieces at the
+            // same points of the section (behind the 2nd, 6th, 10th and 14th MFMA of 16)
+#pragma unroll
+            for (int k2 = 0; k2 < 2; ++k2)
+#pragma unroll
+                for (int cf = 0; cf < 2; ++cf)
+#pragma unroll
+                    for (int pf = 0; pf < 4; ++pf) {
+                        acc16[2 * ni + cf][pf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2 * cf + k2], af[pf >> 1][2 * (pf & 1) + k2],
+                                                                                       acc16[2 * ni + cf][pf], 0, 0, 0);
+                        const int n = 8 * k2 + 4 * cf + pf;
+                        if ((n & 3) == 1 && (n >> 2) < npieces) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (ABL != 5) dma16(g[n >> 2], d[n >> 2]);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+        }
 #if PP_PRIO_MODE == 0
         __builtin_amdgcn_s_setprio(0);
 #endif
@@ -289,10 +328,17 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
     wait_vm<0>();                                        // the tail's zero-fill DMAs target the ring the epilogue overlays
     barrier();
     if (ABL == 6) {
+        if constexpr (MS == 32) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) asm volatile("" ::"v"(acc[ni][mi]));
+        } else {
+#pragma unroll
+            for (int cf = 0; cf < 4; ++cf)
+#pragma unroll
+                for (int pf = 0; pf < 4; ++pf) asm volatile("" ::"v"(acc16[cf][pf]));
+        }
         return;
     }
 
@@ -311,8 +357,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const u32x4 v = {__float_as_uint(acc[ni][mi][4 * g]), __float_as_uint(acc[ni][mi][4 * g + 1]),
-                                     __float_as_uint(acc[ni][mi][4 * g + 2]), __float_as_uint(acc[ni][mi][4 * g + 3])};
+                    // (MS 16: the sixteen f32x4 accumulators in their own order — ni * 2 + mi the channel, g the pixel fragment)
+                    const u32x4 v = MS == 32 ? u32x4{__float_as_uint(acc[ni][mi][4 * g]), __float_as_uint(acc[ni][mi][4 * g + 1]),
+                                                     __float_as_uint(acc[ni][mi][4 * g + 2]), __float_as_uint(acc[ni][mi][4 * g + 3])}
+                                             : __builtin_bit_cast(u32x4, acc16[ni * 2 + mi][g]);
                     __builtin_amdgcn_raw_buffer_store_b128(v, rsP, mine + ((ni * 2 + mi) * 4 + g) * (512 * 16), 0, kSc1);
                 }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's partials are written through
@@ -326,7 +374,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[ni][mi][e] = 0.0f;
+                for (int e = 0; e < 16; ++e) {
+                    if (MS == 32) acc[ni][mi][e] = 0.0f;
+                    else acc16[ni * 2 + mi][e >> 2][e & 3] = 0.0f;
+                }
         // S rounds of 16 loads per lane, the next round in flight while this one is added (a reducing CU pulls S x 128 KB)
         u32x4 va[16], vb[16];
         auto fetch = [&](u32x4 (&v)[16], int sp) {
@@ -343,7 +394,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) acc[ni][mi][4 * g + c] += __uint_as_float(v[(ni * 2 + mi) * 4 + g][c]);
+                        for (int c = 0; c < 4; ++c) {
+                            if (MS == 32) acc[ni][mi][4 * g + c] += __uint_as_float(v[(ni * 2 + mi) * 4 + g][c]);
+                            else acc16[ni * 2 + mi][g][c] += __uint_as_float(v[(ni * 2 + mi) * 4 + g][c]);
+                        }
         };
         fetch(va, 0);
         for (int sp = 0; sp < S; sp += 2) {
@@ -367,18 +421,19 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
         constexpr bool kSilu = kAct && !kKeep, kRes = decltype(res_tag)::value, kD2s = decltype(d2s_tag)::value;
         static_assert(!(kD2s && (kKeep || kAct)), "depth-to-space addressing serves the backward forms only");
         typedef __attribute__((ext_vector_type(2))) float f32x2v;
-        float4 bq[2][4];
+        float4 bq[2][4];                                         // MS 16: bq[0][cb]
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd)
-                bq[ni][qd] = *reinterpret_cast<const float4*>(bias_s + wn * 64 + ni * 32 + 8 * qd + 4 * (lane >> 5));
+                if (MS == 32) bq[ni][qd] = *reinterpret_cast<const float4*>(bias_s + wn * 64 + ni * 32 + 8 * qd + 4 * (lane >> 5));
+                else if (ni == 0) bq[0][qd] = *reinterpret_cast<const float4*>(bias_s + wn * 64 + 16 * qd + 4 * (lane >> 4));
         const int chunk = lane & 7, r0 = lane >> 3;
         const int mrow = m0 + wm * 64 + r0, n = n0 + wn * 64 + chunk * 8;
         unsigned short* const op = a.out + (long)mrow * a.out_cs + n;
         const unsigned short* const rp = kRes ? a.res + (long)mrow * a.res_cs + n : nullptr;
         const long ostep = 8L * a.out_cs, rstep = kRes ? 8L * a.res_cs : 0;
-        unsigned char* const wr = my + (lane & 31) * kEpiPitch + 8 * (lane >> 5);
+        unsigned char* const wr = MS == 32 ? my + (lane & 31) * kEpiPitch + 8 * (lane >> 5) : my + (lane & 15) * kEpiPitch + 8 * (lane >> 4);
         const unsigned char* const rd = my + r0 * kEpiPitch + chunk * 16;
         const int obyte = CHAIN ? (int)(((long)mrow * a.out_cs + n) * 2) : 0;
 #pragma unroll
@@ -406,9 +461,15 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int gid, unsi
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
                     unsigned lo, hi;
+                    if constexpr (MS == 32) {
                     bias_act_pack4<kSilu>(acc[ni][mi][4 * qd], acc[ni][mi][4 * qd + 1], acc[ni][mi][4 * qd + 2], acc[ni][mi][4 * qd + 3],
                                           bq[ni][qd], lo, hi);
                     *reinterpret_cast<u32x2*>(wr + mi * 32 * kEpiPitch + (ni * 32 + 8 * qd) * 2) = u32x2{lo, hi};
+                    } else {                                     // ni: the 16-pixel fragment of the group, qd: the 16-channel fragment
+                        const f32x4 d = acc16[qd][2 * mi + ni];
+                        bias_act_pack4<kSilu>(d[0], d[1], d[2], d[3], bq[0][qd], lo, hi);
+                        *reinterpret_cast<u32x2*>(wr + (2 * mi + ni) * 16 * kEpiPitch + 16 * qd * 2) = u32x2{lo, hi};
+                    }
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave wrote and reads: in-order LDS, no barrier
 #pragma unroll
@@ -500,12 +561,21 @@ __global__ __launch_bounds__(512) void k_conv_pp128(const ConvArgs a) {
     conv_tile<ABL, SPLIT, false>(a, xcd_remap(blockIdx.x, SPLIT ? ntile * a.ksplit : ntile), smem, none);
 }
 
+// the same kernel with the k-loop on v_mfma_f32_16x16x32_bf16 (MS 16)
+template <int ABL, bool SPLIT>
+__global__ __launch_bounds__(512) void k_conv_pp128_m16(const ConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    ChainCtx none{nullptr, -1};
+    const int ntile = a.mtiles * a.ntiles;
+    conv_tile<ABL, SPLIT, false, 16>(a, xcd_remap(blockIdx.x, SPLIT ? ntile * a.ksplit : ntile), smem, none);
+}
+
 #ifndef ADAYOLO_TILE_ONLY
 
-template <int ABL, bool SPLIT = false>
+template <int ABL, bool SPLIT = false, int MS = 32>
 static hipError_t launch(ConvArgs a, hipStream_t s) {
     static_assert(kSmem <= 160 * 1024, "LDS budget");
-    auto kern = k_conv_pp128<ABL, SPLIT>;
+    auto kern = MS == 16 ? k_conv_pp128_m16<ABL, SPLIT> : k_conv_pp128<ABL, SPLIT>;
     static bool configured = false;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -545,19 +615,21 @@ hipError_t launch_conv_pp128_splitk(ConvArgs a, hipStream_t s, int S, void* work
     a.ksplit = S;
     a.tickets = static_cast<int*>(workspace);
     a.partial = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + (tiles * 4 + 1023) / 1024 * 1024);
-    return pp128::launch<0, true>(a, s);
+    return mfma_shape(kShapePp128) == 16 ? pp128::launch<0, true, 16>(a, s) : pp128::launch<0, true>(a, s);
 }
 
 // variant 60 = the kernel; with -DADAYOLO_MEASURE 65 / 66 = measurement builds. hipErrorInvalidValue -> not served.
 hipError_t launch_conv_pp128(ConvArgs a, hipStream_t s, int variant) {
     if (a.Cin % 64 || a.Cout % 128) return hipErrorInvalidValue;
+    const bool m16 = mfma_shape(kShapePp128) == 16;      // read at enqueue time: a captured graph keeps what it captured
 #ifdef ADAYOLO_MEASURE
+    if (m16 && variant == 66) return pp128::launch<6, false, 16>(a, s);
     if (variant == 65) return pp128::launch<5>(a, s);
     if (variant == 66) return pp128::launch<6>(a, s);
     if (variant == 67) return pp128::launch<7>(a, s);
 #endif
     (void)variant;
-    return pp128::launch<0>(a, s);
+    return m16 ? pp128::launch<0, false, 16>(a, s) : pp128::launch<0>(a, s);
 }
 
 #endif  // ADAYOLO_TILE_ONLY

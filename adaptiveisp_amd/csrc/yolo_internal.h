@@ -68,6 +68,11 @@ struct ChainArgs {
     int stagger;                 // cycles: workgroup b starts ((b >> 3) & 7) * stagger late (0: all at once). ADAYOLO_CHAIN_STAGGER
 };
 hipError_t launch_conv_chain(const ChainArgs& c, int grid, hipStream_t s);
+// The MFMA shape the k-loop of a ring-kernel family runs on: 32 (v_mfma_f32_32x32x16_bf16) or 16 (v_mfma_f32_16x16x32_bf16).
+// Process-wide, read by the launchers on the host at enqueue time (adayolo_set_mfma_shape / ADAYOLO_MFMA_SHAPE_PP, _PP128);
+// the chain kernel runs each tile type on its family's shape.
+enum ShapeFamily { kShapePp = 0, kShapePp128 = 1 };
+int mfma_shape(ShapeFamily f);
 hipError_t launch_conv_dma(ConvArgs a, hipStream_t s, int variant);   // LDS-DMA ring (yolo_conv_dma.hip)
 hipError_t launch_conv_dma2(ConvArgs a, hipStream_t s, int variant);  // lean-address 32x32 MFMA ring (yolo_conv_dma2.hip)
 hipError_t launch_conv_small(ConvArgs a, hipStream_t s, int variant); // 3x3, Cin 32/64, whole K resident (yolo_conv_small.hip)

@@ -37,9 +37,25 @@ extern "C" {
 #define ADAYOLO_ELAUNCH -3
 
 /*
+ * The MFMA shape of the k-loop of the two ring-kernel families — family 0: the 256 px x 256 ch kernel (variant 50, chain tile
+ * 0, the first layer of the fused pair), family 1: the 256 px x 128 ch kernel (variant 60, its split-K and training forms,
+ * chain tile 1). shape 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16: the same tiles, ring and schedule, and
+ * results that differ by the summation order inside a k-tile only (two bf16 roundings of the same sum). Process-wide; the
+ * launchers read it on the host when a call enqueues, so a captured graph keeps the kernels it captured and one process can
+ * run both in turn. Initial value: ADAYOLO_MFMA_SHAPE_PP / ADAYOLO_MFMA_SHAPE_PP128 in the environment (16 or 32), else the
+ * built-in default below (the faster by wall time on MI355X: profiles/mfma_shape_ab.txt).
+ * set: 0, or ADAYOLO_EINVAL (family not 0 / 1, shape not 16 / 32). get: the shape, or ADAYOLO_EINVAL.
+ */
+#define ADAYOLO_MFMA_SHAPE_PP_DEFAULT    16
+#define ADAYOLO_MFMA_SHAPE_PP128_DEFAULT 16
+int adayolo_set_mfma_shape(int family, int shape);
+int adayolo_get_mfma_shape(int family);
+
+/*
  * out[b,ho,wo,co] = act( bias[co] + sum_{kh,kw,ci} in[b, ho*stride-pad+kh, wo*stride-pad+kw, ci] * w[co,kh,kw,ci] )
  *                   (+ residual[b,ho,wo,co] if residual != NULL, added AFTER the activation: Bottleneck shortcut)
- * Implicit GEMM on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), fp32 accumulate, fused epilogue.
+ * Implicit GEMM on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16; the two ring-kernel families: the shape selected above),
+ * fp32 accumulate, fused epilogue.
  * ksize in {1,3}; pad = ksize/2; stride in {1,2}. Ho = (H + 2*pad - ksize)/stride + 1 (same for Wo).
  */
 int adayolo_conv_fwd(const void* in, int in_cstride,
