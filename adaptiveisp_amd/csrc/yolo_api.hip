@@ -713,6 +713,15 @@ int adayolo_nms(const float* boxes_xyxy, int n, float iou_thres, int max_det, vo
                            static_cast<hipStream_t>(stream)));
 }
 
+int adayolo_match(const adayolo_match_args* a, void* stream) {
+    if (!a || !a->det || !a->det_offset || !a->iouv || !a->predn || !a->correct) return ADAYOLO_EINVAL;
+    if (a->n_targets < 0 || a->batch < 0 || a->nc < 1 || a->n_iou < 1 || a->n_iou > ADAYOLO_MATCH_MAX_IOU) return ADAYOLO_ESHAPE;
+    if (a->flags & ~ADAYOLO_MATCH_NATIVE) return ADAYOLO_ESHAPE;
+    if ((a->n_targets > 0 && !a->targets) || (!(a->flags & ADAYOLO_MATCH_NATIVE) && !a->geom)) return ADAYOLO_EINVAL;
+    if (a->batch == 0) return ADAYOLO_OK;
+    return code(launch_match(*a, static_cast<hipStream_t>(stream)));
+}
+
 static int detloss_check(const adayolo_loss_args* a, bool bwd) {
     if (!a || a->nl < 1 || a->nl > 4 || a->B < 1 || a->B > 65535 || a->na < 1 || a->nc < 1 || a->no != a->nc + 5 || !a->loss || !a->ticket)
         return ADAYOLO_EINVAL;

@@ -115,5 +115,6 @@ hipError_t launch_detloss_fwd(const adayolo_loss_args& a, hipStream_t s);   // y
 hipError_t launch_detloss_bwd(const adayolo_loss_args& a, hipStream_t s);
 hipError_t launch_nms(const float* boxes, int n, float thr, int max_det, unsigned long long* mask_ws, int* keep,
                       int* num_keep, hipStream_t s);
+hipError_t launch_match(const adayolo_match_args& a, hipStream_t s);          // yolo_match.hip
 
 }  // namespace adayolo

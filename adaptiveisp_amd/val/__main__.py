@@ -6,7 +6,7 @@ Images go through data.ImageFolderSource (one pass in file order; `lod`: /255, `
 device), `--batch-size` at a time with the last, partial batch evaluated on a detector engine of its own; the ISP
 episode, the detector, NMS, matching and mAP are val.run_eval's. Everything is written under the run directory
 (`--project`/`--name`, incremented as exp, exp2, ...): records.txt, results.json, and on request param_results/,
-img_results/step-<i>/, labels/<stem>.txt and <detector stem>_predictions.json (val/writers.py)."""
+img_results/step-<i>/, labels/<stem>.txt, <detector stem>_predictions.json and confusion_matrix.csv (val/writers.py)."""
 import argparse
 import json
 import math
@@ -105,6 +105,10 @@ def build_parser():
     ap.add_argument("--name", default="exp")
     ap.add_argument("--exist-ok", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay each batch's ISP episode + detector as one hipGraph")
+    ap.add_argument("--match", default="host", choices=("host", "device"),
+                    help="where detections are matched to labels: host (torch, per image) or device (one HIP launch per batch)")
+    ap.add_argument("--confusion", action="store_true",
+                    help="confusion_matrix.csv (conf 0.25, IoU 0.45); with --verbose also its per-class counts")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tune-cache", default=None, help="detector engine autotune cache (JSON)")
     ap.add_argument("--workers", type=int, default=4, help="decoding threads")
@@ -262,7 +266,8 @@ def main(argv=None):
                        pipeline=a.pipeline, records_path=os.path.join(save_dir, "records.txt"), nc=nc,
                        param_dir=os.path.join(save_dir, "param_results") if a.save_param else None, graph=a.graph,
                        image_dir=image_dir, image_writer=writer,
-                       on_image=on_image if (a.save_txt or a.save_json) else None)
+                       on_image=on_image if (a.save_txt or a.save_json) else None, match=a.match,
+                       confusion=True if a.confusion else None)
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
         finished = True
@@ -288,6 +293,14 @@ def main(argv=None):
     if (a.verbose or nc < 50) and nc > 1:
         for row in rows:
             print(ROW % (row["name"], row["images"], row["instances"], row["p"], row["r"], row["ap50"], row["ap75"], row["ap"]))
+    if a.confusion:
+        cmat = res["confusion"]
+        writers.save_confusion_csv(cmat, names, os.path.join(save_dir, "confusion_matrix.csv"))
+        if a.verbose:
+            print(("%22s" + "%11s" * 4) % ("Class", "Correct", "As other", "Backgr.", "Missed"))
+            for c in range(nc):
+                print(("%22s" + "%11i" * 4) % (names.get(c, str(c)), cmat[c, c], cmat[c, :nc].sum() - cmat[c, c], cmat[c, nc],
+                                               cmat[nc, c]))
     ms = dt / max(seen, 1) * 1e3
     print(f"Speed: {ms:.1f} ms per image (ISP episode, detector, NMS, matching; data loading included) at shape "
           f"{(a.batch_size, 3, a.img_size, a.img_size)}")

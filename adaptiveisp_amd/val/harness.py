@@ -11,7 +11,7 @@ import torch
 from .. import _lib
 from ..util import STATE_STOPPED_DIM
 from .boxes import scale_boxes, xywh2xyxy
-from .metrics import ap_per_class, process_batch
+from .metrics import ConfusionMatrix, ap_per_class, match_batch, process_batch
 from .nms import non_max_suppression
 
 
@@ -117,7 +117,7 @@ class _EpisodeGraph:
 
 def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False,
              pipeline=None, records_path=None, nc=80, nms_fn=None, param_dir=None, details=None, graph=False,
-             image_dir=None, image_writer=None, on_image=None):
+             image_dir=None, image_writer=None, on_image=None, match="host", confusion=None):
     """Returns dict(mp, mr, map50, map75, map, seen, nt, ap_class, ap, records). `detector(x)` -> [B, N, 5+nc]
     decoded predictions (YoloEngine or the module tree in eval mode). `pipeline`: optional list of forced filter ids
     per step (val_adaptiveisp.py:292, --pipeline). `param_dir`: write one JSON per batch (named after its first image) with
@@ -132,11 +132,26 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
     its own, joined before returning). The eager loop then runs even with `graph`: the replay keeps no per-step images.
     `on_image(path, predn, shape)`: called for every image with detections, with them in native image space (xyxy, conf,
     class; a host tensor) and its native (h, w): where the reference saves --save-txt / --save-json (:371-374).
-    The result also holds per-class precision `p` and recall `r` (rows in `ap_class` order)."""
+    The result also holds per-class precision `p` and recall `r` (rows in `ap_class` order).
+    `match`: "host" (the default: scale_boxes / process_batch per image, as the reference's loop) or "device" (HIP device only):
+    the NMS outputs of a batch are concatenated once, the per-image geometry and row offsets go up in one pinned copy, and ONE
+    `adayolo_match` launch maps detections and labels to native space and fills `correct` for every image; `stats`, `details`,
+    `on_image` and `single_cls` read slices of its outputs. NOT bit for bit the results of match="host" on a HIP device:
+    the kernel divides by the gain, as the host path does on CPU tensors, while torch on a HIP device divides a tensor by a
+    Python scalar through the reciprocal. Unless 1 / gain is exact (gain 1, 0.5, ...), native-space boxes can therefore differ
+    from the default mode's in their last bit (never more: tests/test_gpu_match.py), and a detection whose IoU sits within that
+    of a level can change its `correct` entry there. The device mode is the one that agrees with a CPU run of the loop.
+    `confusion`: True (a ConfusionMatrix(nc) of the defaults) or a ConfusionMatrix to add to — filled per image on the host,
+    or inside the same launch with match="device"; the result then gains `confusion`, its integer [nc+1, nc+1] matrix."""
     import collections
     import json
     from ..util import get_initial_states, get_noise, to_device_async
     dev = next(agent.parameters()).device
+    if match not in ("host", "device"):
+        raise ValueError(f"match={match!r}: expected 'host' or 'device'")
+    if match == "device" and dev.type != "cuda":
+        raise ValueError(f"match='device' runs the adayolo_match kernel and needs a HIP device; the agent is on '{dev}'")
+    cm = ConfusionMatrix(nc) if confusion is True else (confusion or None)
     iouv = torch.linspace(0.5, 0.95, 10, device=dev)
     niou = iouv.numel()
     stats, records, seen = [], [], 0
@@ -225,6 +240,9 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
             records.append((os.path.split(str(paths[b]))[1], row))
         preds = non_max_suppression(preds, conf_thres, iou_thres, multi_label=True, agnostic=single_cls,
                                     max_det=max_det, nms_fn=nms_fn)
+        if match == "device":
+            back_device(preds, im, targets, paths, shapes, retouch)
+            preds = []
         for si, pred in enumerate(preds):
             labels = targets[targets[:, 0] == si, 1:]
             nl, npr = labels.shape[0], pred.shape[0]
@@ -237,6 +255,8 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
             if npr == 0:
                 if nl:
                     stats.append((correct, *torch.zeros((2, 0), device=dev), labels[:, 0]))
+                    if cm is not None:
+                        cm.process_batch(None, labels[:, 0])
                 continue
             if single_cls:
                 pred[:, 5] = 0
@@ -247,6 +267,8 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
                 scale_boxes(im[si].shape[1:], tbox, shape, shapes[si][1])
                 labelsn = torch.cat((labels[:, 0:1], tbox), 1)
                 correct = process_batch(predn, labelsn, iouv)
+                if cm is not None:
+                    cm.process_batch(predn, labelsn)
             if details is not None:
                 details[-1]["correct"] = correct.detach().cpu()
             if on_image is not None:
@@ -254,6 +276,50 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
             stats.append((correct, pred[:, 4], pred[:, 5], labels[:, 0]))
         if slot is not None:
             _EpisodeGraph.release(slot)
+
+    def back_device(preds, im, targets, paths, shapes, retouch):
+        """The matching of one batch as ONE launch (match="device"): what the loop over the images in `back` does."""
+        nonlocal seen
+        nb = len(preds)
+        counts = [int(p.shape[0]) for p in preds]
+        if details is not None:
+            for si, pred in enumerate(preds):
+                details.append(dict(path=str(paths[si]), retouch=retouch[si].detach().cpu(), pred=pred.detach().cpu().clone(),
+                                    correct=None))
+        seen += nb
+        det = torch.cat(preds, 0) if nb > 1 else preds[0]
+        if single_cls:
+            det[:, 5] = 0
+        # per image (gain, pad_x, pad_y, h0, w0) and the row offsets: one pinned buffer, one asynchronous copy
+        host = np.zeros(nb * 5 + nb + 1, np.int32)
+        geom = host[:nb * 5].view(np.float32).reshape(nb, 5)
+        h1, w1 = im.shape[2:]
+        for si in range(nb):
+            (h0, w0), ratio_pad = shapes[si][0], shapes[si][1]
+            if ratio_pad is None:                                  # the arithmetic of scale_boxes
+                gain = min(h1 / h0, w1 / w0)
+                pad = (w1 - w0 * gain) / 2, (h1 - h0 * gain) / 2
+            else:
+                gain, pad = ratio_pad[0][0], ratio_pad[1]
+            geom[si] = (gain, pad[0], pad[1], h0, w0)
+        host[nb * 5 + 1:] = np.cumsum(counts)
+        up = to_device_async(host, dev)
+        args = (det, up[nb * 5:], targets, up[:nb * 5].view(torch.float32).view(nb, 5), iouv)
+        predn, correct = cm.process_batch_device(*args) if cm is not None else match_batch(*args, nc)
+        correct = correct.bool()
+        if det.shape[0] or targets.shape[0]:
+            # (an image with neither detections nor labels adds nothing on the host path either; the target classes of a batch
+            # are counted whatever their order)
+            stats.append((correct, det[:, 4], det[:, 5], targets[:, 1]))
+        if det.shape[0] and (details is not None or on_image is not None):
+            predn_h, correct_h, start = predn.cpu(), correct.cpu(), 0
+            for si, k in enumerate(counts):
+                if k:
+                    if details is not None:
+                        details[si - nb]["correct"] = correct_h[start:start + k].clone()
+                    if on_image is not None:
+                        on_image(str(paths[si]), predn_h[start:start + k].clone(), shapes[si][0])
+                start += k
 
     # Graph mode is a two-stage pipeline over the batches: the replay of batch i + 1 (a side stream) runs while the host works
     # through NMS / matching of batch i (round 6: at batch 1 the loop was 1.8 ms of replay + 2.4 ms of host-bound NMS and matching
@@ -288,6 +354,8 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
         res.update(mp=float(p.mean()), mr=float(r.mean()), map50=float(ap[:, 0].mean()), map75=float(ap[:, 5].mean()),
                    map=float(ap.mean(1).mean()), ap=ap, ap_class=ap_class, p=p, r=r)
     res["nt"] = np.bincount(stats[3].astype(int), minlength=nc) if len(stats) else np.zeros(nc, int)
+    if cm is not None:
+        res["confusion"] = cm.matrix
     if records_path:
         with open(records_path, "w") as f:                         # val_adaptiveisp.py:269-322 "records.txt"
             f.write(",".join(filter_names) + "\n")

@@ -8,7 +8,12 @@ tests/golden/evalharness.npz — but organised around what the computation IS ra
     IoU level), and a label keeps the lowest-index detection that claims it — so all 10 levels come from one arg-max and
     one scatter-min instead of a per-level sort / unique / unique;
   * AP: detections are grouped by class with one stable sort; per-class cumulative TP/FP are segment cumsums over the
-    whole array (exact integers), all IoU levels at once; only numpy's own interpolation runs per class.
+    whole array (exact integers), all IoU levels at once; only numpy's own interpolation runs per class;
+  * confusion matrix (`ConfusionMatrix`, the reference's utils/metrics.py:126-184 without its plot): a detection claims its
+    best label of ANY class, a label credits its best claimant — two arg-maxes instead of two sort / unique rounds.
+
+`match_batch` / `ConfusionMatrix.process_batch_device` run the matching of a whole batch — the map to native image space, the
+`correct` matrix at every level and the confusion counts — as one HIP launch (csrc/yolo_match.hip, `adayolo_match`).
 """
 import numpy as np
 import torch
@@ -45,6 +50,110 @@ def process_batch(detections, labels, iouv):
     first.scatter_reduce_(0, best_label[:, None].expand(N, T), torch.where(claims, det_index, N), reduce="amin")
     credited = claims & (first[best_label] == det_index)
     return credited.to(iouv.device)
+
+
+def match_batch(det, det_offset, targets, geom, iouv, nc, native=False, confusion=None, cm_conf=0.25, cm_iou=0.45):
+    """The matching of a whole batch as ONE launch of `adayolo_match` (HIP device tensors only; include/adayolo.h has the
+    argument layout): det [K,6] post-NMS rows of all images, image-major; det_offset int32 [B+1]; targets [n,6] (image, class,
+    x, y, w, h in network-input pixels, any row order); geom fp32 [B,5] (gain, pad_x, pad_y, h0, w0); iouv [T] on the device.
+    -> (predn [K,6] native-space detections, correct uint8 [K,T]). `confusion`: an int32 [(nc+1)*(nc+1)] device tensor the
+    confusion counts are ADDED to (ConfusionMatrix.process_batch_device hands over its own). `native`: boxes (det and target
+    columns 2..5, xyxy) are in native space already — nothing is scaled or clipped, `geom` may be None."""
+    from ..yolo import _lib
+    return _lib.match(det, det_offset, targets, geom, iouv, nc, native=native, confusion=confusion, cm_conf=cm_conf,
+                      cm_iou=cm_iou)
+
+
+class ConfusionMatrix:
+    """What the detector confuses with what: `matrix[p, t]` counts detections of class p credited to labels of class t, index
+    `nc` being background — `matrix[nc, t]`: labels of class t nothing was credited to (missed), `matrix[p, nc]`: detections of
+    class p credited to no label. Same counts as the reference's ConfusionMatrix.process_batch (utils/metrics.py:134-178).
+
+    Rule, per image: of the detections with conf > `conf`, each claims the label it has the highest IoU with — whatever the
+    classes — if that IoU is > `iou_thres`; a label credits the claimant with the highest IoU (matrix[det class, label class]
+    += 1); a label nobody claims is a background miss; if the image has at least one claim, every kept detection that was not
+    credited is a background prediction — with no claim at all the detections add nothing (the reference's behaviour, :166-178).
+
+    Ties are OUR definition, not the reference's (which leaves them to numpy's unstable argsort()[::-1]): of equal IoUs the
+    lowest label index, then the lowest detection index, wins.
+
+    Counts made on the host (`process_batch`) and on the device (`process_batch_device`, inside the `adayolo_match` launch)
+    add up in `.matrix`; the device counts are read back lazily, once, when `.matrix` is next asked for."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45):
+        self.nc, self.conf, self.iou_thres = int(nc), conf, iou_thres
+        self._host = np.zeros((self.nc + 1, self.nc + 1), np.int64)
+        self._dev = self._dev_host = None                    # int32 device counts; their host copy (None: stale)
+
+    @property
+    def matrix(self):
+        """Integer [nc+1, nc+1], row = predicted, column = true, index nc = background (a copy: later counts do not
+        change an array handed out earlier)."""
+        if self._dev is None:
+            return self._host.copy()
+        if self._dev_host is None:
+            self._dev_host = self._dev.cpu().numpy().astype(np.int64).reshape(self.nc + 1, self.nc + 1)
+        return self._host + self._dev_host
+
+    def process_batch(self, detections, labels):
+        """detections [N,6] (xyxy, conf, class) or None, labels [M,5] (class, xyxy) in the same space — with
+        `detections=None` a plain vector of label classes will do: every label is a background miss."""
+        nc = self.nc
+        labels = torch.as_tensor(labels).detach().cpu()
+        if detections is None:
+            gt = (labels[:, 0] if labels.ndim == 2 else labels).int().numpy()
+            np.add.at(self._host, (nc, gt), 1)
+            return
+        detections = torch.as_tensor(detections).detach().cpu()
+        detections = detections[detections[:, 4] > self.conf]
+        N, M = detections.shape[0], labels.shape[0]
+        gt, dc = labels[:, 0].int().numpy(), detections[:, 5].int().numpy()
+        if M == 0:
+            return
+        if N == 0:
+            np.add.at(self._host, (nc, gt), 1)
+            return
+        iou = box_iou(labels[:, 1:], detections[:, :4])                               # [M,N]
+        best_iou = iou.max(dim=0).values                                              # per detection, over ALL labels
+        label_index = torch.arange(M)[:, None].expand(M, N)
+        best_label = torch.where(iou == best_iou[None, :], label_index, M).amin(dim=0)    # ties: lowest label index
+        claims = best_iou > self.iou_thres
+        # per label: the claimant with the highest IoU, ties to the lowest detection index
+        top = torch.full((M,), -1.0).scatter_reduce_(0, best_label, torch.where(claims, best_iou, -1.0), reduce="amax")
+        wins = claims & (best_iou == top[best_label])
+        det_index = torch.arange(N)
+        first = torch.full((M,), N, dtype=torch.int64).scatter_reduce_(0, best_label, torch.where(wins, det_index, N),
+                                                                        reduce="amin")
+        credited = (wins & (first[best_label] == det_index)).numpy()
+        bl = best_label.numpy()
+        np.add.at(self._host, (dc[credited], gt[bl[credited]]), 1)
+        missed = np.ones(M, bool)
+        missed[bl[credited]] = False
+        np.add.at(self._host, (nc, gt[missed]), 1)
+        if claims.any():
+            np.add.at(self._host, (dc[~credited], nc), 1)
+
+    def process_batch_device(self, det, det_offset, targets, geom, iouv, native=False):
+        """A whole batch inside the matching launch (`match_batch`'s arguments): the counts are added to a device matrix of
+        this object's. -> (predn, correct) as match_batch."""
+        if self._dev is None or self._dev.device != det.device:
+            if self._dev is not None:                        # counts made on another device move to the host side
+                self._host = self.matrix.copy()
+            self._dev = torch.zeros((self.nc + 1) * (self.nc + 1), dtype=torch.int32, device=det.device)
+        self._dev_host = None
+        return match_batch(det, det_offset, targets, geom, iouv, self.nc, native=native, confusion=self._dev,
+                           cm_conf=self.conf, cm_iou=self.iou_thres)
+
+    def tp_fp(self):
+        """(true positives, false positives) per class, background left out."""
+        m = self.matrix
+        tp = m.diagonal()
+        return tp[:-1], (m.sum(1) - tp)[:-1]
+
+    def normalized(self):
+        """Every column divided by its sum + 1e-9: what the reference's plot draws."""
+        m = self.matrix
+        return m / (m.sum(0).reshape(1, -1) + 1e-9)
 
 
 def smooth(y, f=0.05):

@@ -17,6 +17,7 @@ from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
+import numpy as np
 import torch
 
 # COCO's 91 category ids minus the 11 that the 2014/2017 annotations never use (12, 26, 29, 30, 45, 66, 68, 69, 71, 83, 91):
@@ -111,3 +112,17 @@ class ImageWriter:
             first = first or e
         if first is not None and raise_errors:
             raise first
+
+
+def save_confusion_csv(matrix, names, file):
+    """confusion_matrix.csv: a header row (`predicted/true`, the class names, `background`), then one row per predicted
+    class and the `background` row (missed labels), integer counts. `names`: {class id: name} or a sequence; a class
+    without a name is written as its number."""
+    matrix = np.asarray(matrix)
+    nc = matrix.shape[0] - 1
+    get = names.get if isinstance(names, dict) else (lambda c, d: names[c] if c < len(names) else d)
+    cols = [str(get(c, str(c))).replace(",", " ") for c in range(nc)] + ["background"]
+    with open(file, "w") as f:
+        f.write(",".join(["predicted/true"] + cols) + "\n")
+        for name, row in zip(cols, matrix):
+            f.write(",".join([name] + [str(int(v)) for v in row]) + "\n")

@@ -7,9 +7,9 @@ import torch
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ADAYOLO_LIB: another BUILD of the same library (measurement builds of tools/build_variant.py); never a fallback
 LIB_PATH = os.environ.get("ADAYOLO_LIB") or os.path.join(_HERE, "csrc", "libadayolo.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 ACT_NONE, ACT_SILU = 0, 1
-EXPORTS = ("adayolo_conv_fwd", "adayolo_conv_fwd_variant", "adayolo_conv_fused1x1_fwd", "adayolo_conv1x1_stream_fwd", "adayolo_bottleneck256_fwd", "adayolo_bottleneck_ws_fwd", "adayolo_conv_keep_fwd", "adayolo_conv_splitk_fwd", "adayolo_conv_dsilu_fwd", "adayolo_conv_s2grad_fwd", "adayolo_conv_splitk_workspace_bytes", "adayolo_conv_chain_workspace_bytes", "adayolo_conv_chain_prepare", "adayolo_conv_chain_fwd", "adayolo_conv_chain_status", "adayolo_conv_chain_poll", "adayolo_conv_chain_tables", "adayolo_stem_fwd", "adayolo_upsample2x", "adayolo_detect_decode", "adayolo_nms", "adayolo_nms_workspace_bytes", "adayolo_stem_fwd_act", "adayolo_stem_keep_fwd", "adayolo_stem_down_fwd", "adayolo_letterbox_pack", "adayolo_silu_fwd", "adayolo_silu_bwd",
+EXPORTS = ("adayolo_conv_fwd", "adayolo_conv_fwd_variant", "adayolo_conv_fused1x1_fwd", "adayolo_conv1x1_stream_fwd", "adayolo_bottleneck256_fwd", "adayolo_bottleneck_ws_fwd", "adayolo_conv_keep_fwd", "adayolo_conv_splitk_fwd", "adayolo_conv_dsilu_fwd", "adayolo_conv_s2grad_fwd", "adayolo_conv_splitk_workspace_bytes", "adayolo_conv_chain_workspace_bytes", "adayolo_conv_chain_prepare", "adayolo_conv_chain_fwd", "adayolo_conv_chain_status", "adayolo_conv_chain_poll", "adayolo_conv_chain_tables", "adayolo_stem_fwd", "adayolo_upsample2x", "adayolo_detect_decode", "adayolo_nms", "adayolo_nms_workspace_bytes", "adayolo_match", "adayolo_stem_fwd_act", "adayolo_stem_keep_fwd", "adayolo_stem_down_fwd", "adayolo_letterbox_pack", "adayolo_silu_fwd", "adayolo_silu_bwd",
            "adayolo_zero_insert2x", "adayolo_upsample2x_bwd", "adayolo_image_grad", "adayolo_detloss_fwd", "adayolo_detloss_bwd",
            "adayolo_strerror", "adayolo_set_mfma_shape", "adayolo_get_mfma_shape",
            "adayolo_abi_version")
@@ -42,6 +42,17 @@ class LossArgs(ctypes.Structure):                  # adayolo_loss_args
                 ("hyp_cls", ctypes.c_float), ("cp", ctypes.c_float), ("cn", ctypes.c_float), ("cls_pw", ctypes.c_float),
                 ("obj_pw", ctypes.c_float), ("loss", ctypes.c_void_p), ("ticket", ctypes.c_void_p),
                 ("grad_loss", ctypes.c_void_p)]
+
+
+class MatchArgs(ctypes.Structure):                 # adayolo_match_args
+    _fields_ = [("det", ctypes.c_void_p), ("det_offset", ctypes.c_void_p), ("targets", ctypes.c_void_p),
+                ("n_targets", ctypes.c_int32), ("batch", ctypes.c_int32), ("geom", ctypes.c_void_p), ("iouv", ctypes.c_void_p),
+                ("n_iou", ctypes.c_int32), ("nc", ctypes.c_int32), ("flags", ctypes.c_int32), ("cm_conf", ctypes.c_float),
+                ("cm_iou", ctypes.c_float), ("predn", ctypes.c_void_p), ("correct", ctypes.c_void_p),
+                ("confusion", ctypes.c_void_p)]
+
+
+MATCH_NATIVE = 1
 
 
 def load():
@@ -113,6 +124,8 @@ def load():
     L.adayolo_conv_chain_poll.restype = ci
     L.adayolo_nms_workspace_bytes.argtypes = [ci]
     L.adayolo_nms_workspace_bytes.restype = ctypes.c_size_t
+    L.adayolo_match.argtypes = [ctypes.POINTER(MatchArgs), vp]
+    L.adayolo_match.restype = ci
     L.adayolo_set_mfma_shape.argtypes = [ci, ci]
     L.adayolo_set_mfma_shape.restype = ci
     L.adayolo_get_mfma_shape.argtypes = [ci]
@@ -135,3 +148,47 @@ def check(rc, what):
 
 def stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _f32(t, what, cols=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise AdayoloError(f"adayolo_match: {what} must be a HIP device tensor: there is no CPU path")
+    t = t.to(torch.float32).contiguous()
+    if cols is not None and (t.ndim != 2 or t.shape[1] != cols):
+        raise AdayoloError(f"adayolo_match: {what} must be [n, {cols}], got {tuple(t.shape)}")
+    return t
+
+
+def match(det, det_offset, targets, geom, iouv, nc, native=False, confusion=None, cm_conf=0.25, cm_iou=0.45):
+    """adayolo_match (include/adayolo.h) on the current stream: det [K,6], det_offset int32 [B+1], targets [n,6], geom [B,5] (None
+    with `native`), iouv [T], all on one HIP device -> (predn fp32 [K,6], correct uint8 [K,T]). `confusion`: int32
+    [(nc+1)*(nc+1)] device tensor, added to. One launch, no host synchronisation."""
+    det, targets, iouv = _f32(det, "det", 6), _f32(targets, "targets", 6), _f32(iouv, "iouv")
+    dev = det.device
+    if det_offset.dtype != torch.int32 or det_offset.device != dev or det_offset.ndim != 1 or det_offset.numel() < 1:
+        raise AdayoloError("adayolo_match: det_offset must be an int32 [B+1] tensor on det's device")
+    det_offset = det_offset.contiguous()
+    B, K, T = det_offset.numel() - 1, det.shape[0], iouv.numel()
+    a = MatchArgs()
+    if not native:
+        geom = _f32(geom, "geom", 5)
+        if geom.shape[0] != B:
+            raise AdayoloError(f"adayolo_match: geom has {geom.shape[0]} rows for {B} images")
+        a.geom = geom.data_ptr()
+    if confusion is not None:
+        if confusion.dtype != torch.int32 or confusion.device != dev or not confusion.is_contiguous() or \
+                confusion.numel() != (nc + 1) * (nc + 1):
+            raise AdayoloError("adayolo_match: confusion must be a contiguous int32 [(nc+1)*(nc+1)] tensor on det's device")
+        a.confusion = confusion.data_ptr()
+    # (an empty tensor has no address; the entry wants one even when no image has a detection: the buffers get one row, and with
+    # K == 0 the output buffer stands in for `det` — no image owns a row, so none is read or written)
+    predn = torch.empty((max(K, 1), 6), dtype=torch.float32, device=dev)
+    correct = torch.empty((max(K, 1), T), dtype=torch.uint8, device=dev)
+    a.det = det.data_ptr() if K else predn.data_ptr()
+    a.det_offset, a.targets, a.n_targets, a.batch = det_offset.data_ptr(), targets.data_ptr() or None, targets.shape[0], B
+    a.iouv, a.n_iou, a.nc, a.flags = iouv.data_ptr(), T, int(nc), MATCH_NATIVE if native else 0
+    a.cm_conf, a.cm_iou, a.predn, a.correct = float(cm_conf), float(cm_iou), predn.data_ptr(), correct.data_ptr()
+    with torch.cuda.device(dev):
+        rc = load().adayolo_match(ctypes.byref(a), stream_ptr())
+    check(rc, "adayolo_match")
+    return predn[:K], correct[:K]

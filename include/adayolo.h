@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define ADAYOLO_ABI_VERSION 9
+#define ADAYOLO_ABI_VERSION 10
 
 #define ADAYOLO_ACT_NONE 0
 #define ADAYOLO_ACT_SILU 1
@@ -343,6 +343,44 @@ int adayolo_detect_decode(const void* raw, int raw_cstride, float* pred, int pre
 size_t adayolo_nms_workspace_bytes(int n);
 int adayolo_nms(const float* boxes_xyxy, int n, float iou_thres, int max_det, void* workspace,
                 int32_t* keep, int32_t* num_keep, void* stream);
+
+/*
+ * Detection / label matching of the eval harness for a whole batch, ONE launch (csrc/yolo_match.hip): what
+ * val/harness.py otherwise does per image with scale_boxes, xywh2xyxy, process_batch and ConfusionMatrix.process_batch
+ * (val/boxes.py, val/metrics.py) — the same fp32 operations in the same order, so every output equals the host path's.
+ *   predn   = clip((xyxy - pad) / gain) to [0, w0] x [0, h0]; the labels go xywh -> xyxy (x -+ w/2), then the same map.
+ *   correct[d][t] = 1: detection d is the lowest-index one among those whose best same-class label (highest IoU,
+ *             lowest label index on equal IoUs) is this label and whose IoU with it is >= iouv[t].
+ *   confusion (row = predicted class, column = true class, index nc = background; ADDED to, so the caller zeroes it once):
+ *             a detection with conf > cm_conf claims the label of any class it has the highest IoU with if that IoU is
+ *             > cm_iou; a label credits its claimant with the highest IoU (then the lowest index): [det class][label class]
+ *             += 1; a label without claimant: [nc][label class] += 1; if the image has a claim at all, every other such
+ *             detection: [det class][nc] += 1. A class outside [0, nc) has no cell: a count that would land in its row or
+ *             column is dropped, and nothing else changes (its claims and credits still are claims and credits). While the launch runs, a
+ *             [class][nc] entry may pass through a value below its final one (a credit is taken from it before all
+ *             detections are added): read the buffer in stream order.
+ * No host synchronisation, no workspace; no cap on detections or labels per image (one workgroup per image).
+ * ADAYOLO_EINVAL: a null pointer (geom may be null with ADAYOLO_MATCH_NATIVE, targets with n_targets == 0, confusion
+ * always; det / predn / correct must be valid addresses even when no image has a detection). ADAYOLO_ESHAPE: n_iou
+ * outside 1..ADAYOLO_MATCH_MAX_IOU, nc < 1, a negative count, unknown flags. batch == 0 returns 0 without a launch.
+ */
+#define ADAYOLO_MATCH_NATIVE  1   /* det rows and target columns 2..5 are native-space xyxy already: no scaling, no clipping */
+#define ADAYOLO_MATCH_MAX_IOU 16
+typedef struct adayolo_match_args {
+    const float*   det;          /* [K][6] xyxy, conf, class: post-NMS rows of all images, image-major */
+    const int32_t* det_offset;   /* [B+1]: image b owns rows det_offset[b] .. det_offset[b+1] */
+    const float*   targets;      /* [n][6] image, class, x, y, w, h in network-input pixels; image b's labels are
+                                    the rows with column 0 == b, in row order (no sorting required of the caller) */
+    int32_t        n_targets, batch;
+    const float*   geom;         /* [B][5] gain, pad_x, pad_y, h0, w0 (fp32) - what scale_boxes uses */
+    const float*   iouv;         /* [T] ascending IoU levels ON THE DEVICE (the harness's own tensor), T <= 16 */
+    int32_t        n_iou, nc, flags;   /* ADAYOLO_MATCH_NATIVE: boxes are native already, no scaling, no clipping */
+    float          cm_conf, cm_iou;
+    float*         predn;        /* [K][6] out: native-space detections (columns 4, 5 copied) */
+    uint8_t*       correct;      /* [K][T] out, 0 / 1 */
+    int32_t*       confusion;    /* [(nc+1)*(nc+1)] accumulated into (caller zeroes it once); NULL: skip */
+} adayolo_match_args;
+int adayolo_match(const adayolo_match_args* args, void* stream);
 
 /*
  * Per-image detection loss of the RL reward on the RAW head maps, with its gradient (training path). Replaces the
