@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_resize_u8", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -69,6 +69,10 @@ def load():
     L.adaisp_unprocess_bayer.restype = ci
     L.adaisp_demosaic_rects.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
     L.adaisp_demosaic_rects.restype = ci
+    L.adaisp_demosaic_ex.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
+    L.adaisp_demosaic_ex.restype = ci
+    L.adaisp_demosaic_rects_ex.argtypes = [vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
+    L.adaisp_demosaic_rects_ex.restype = ci
     sz = ctypes.c_size_t
     L.adaisp_resize_u8.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, ci, ci, vp]
     L.adaisp_resize_u8.restype = ci
@@ -284,11 +288,19 @@ def pool64_backward(grad_pooled, H, W):
 
 
 CFA = {"RGGB": 0, "GRBG": 1, "GBRG": 2, "BGGR": 3}
+DEMOSAIC = {"bilinear": 0, "mhc": 1}    # ADAISP_DEMOSAIC_*: 3 x 3 bilinear; 5 x 5 gradient-corrected (Malvar-He-Cutler)
 
 
-def demosaic(raw, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None):
-    """Bayer front-end: raw uint16 [B,H,W] on the device -> planar fp32 [B,3,H,W] in [0,1] (include/adaisp.h)."""
-    L = load()
+def _method(what, method):
+    if not isinstance(method, str) or method not in DEMOSAIC:
+        raise AdaispError(f"{what}: method must be one of {sorted(DEMOSAIC)}, got {method!r}")
+    return DEMOSAIC[method]
+
+
+def demosaic(raw, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None, method="bilinear"):
+    """Bayer front-end: raw uint16 [B,H,W] on the device -> planar fp32 [B,3,H,W] in [0,1] (include/adaisp.h); `method`
+    "bilinear" or "mhc" (adaisp_demosaic_ex; "mhc" is not clamped and can leave [0,1] at edges)."""
+    L, meth = load(), _method("demosaic", method)
     if raw.device.type != "cuda":
         raise AdaispError("demosaic: raw must live on a HIP device (there is no CPU path)")
     if raw.dtype not in (torch.uint16, torch.int16) or raw.dim() != 3:
@@ -299,9 +311,9 @@ def demosaic(raw, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=raw.device)
     pat = CFA[pattern.upper()] if isinstance(pattern, str) else int(pattern)
     with torch.cuda.device(raw.device):
-        rc = L.adaisp_demosaic(raw.data_ptr(), out.data_ptr(), B, H, W, pat, float(black_level), float(white_level),
-                               _stream())
-    _check(rc, "adaisp_demosaic")
+        rc = L.adaisp_demosaic_ex(raw.data_ptr(), out.data_ptr(), B, H, W, pat, meth, float(black_level),
+                                  float(white_level), _stream())
+    _check(rc, "adaisp_demosaic_ex")
     _wrote(out)
     return out
 
@@ -372,10 +384,11 @@ def unprocess_bayer(src, desc, S, seed=0, flags=0, pattern="RGGB", black_level=0
     return out
 
 
-def demosaic_rects(raw, desc, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None):
-    """adaisp_demosaic_rects: the letterboxed uint16 [B,S,S] plane of `unprocess_bayer` and its descriptors -> planar fp32
-    [B,3,S,S]: `demosaic` inside every image's own rectangle (phase and mirror at the rectangle), exactly 0 outside."""
-    L = load()
+def demosaic_rects(raw, desc, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None, method="bilinear"):
+    """adaisp_demosaic_rects_ex: the letterboxed uint16 [B,S,S] plane of `unprocess_bayer` and its descriptors -> planar
+    fp32 [B,3,S,S]: `demosaic` (same `method`) inside every image's own rectangle (phase and mirror at the rectangle),
+    exactly 0 outside."""
+    L, meth = load(), _method("demosaic_rects", method)
     if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda":
         raise AdaispError("demosaic_rects: raw must be a HIP device tensor (there is no CPU path)")
     B = _bytes_on_device("demosaic_rects", ((desc, "desc"),))
@@ -390,9 +403,9 @@ def demosaic_rects(raw, desc, pattern="RGGB", black_level=0.0, white_level=65535
           or not out.is_contiguous() or out.device != raw.device):
         raise AdaispError(f"demosaic_rects: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {raw.device}")
     with torch.cuda.device(raw.device):
-        rc = L.adaisp_demosaic_rects(raw.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, _pattern(pattern),
-                                     float(black_level), float(white_level), _stream())
-    _check(rc, "adaisp_demosaic_rects")
+        rc = L.adaisp_demosaic_rects_ex(raw.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, _pattern(pattern), meth,
+                                        float(black_level), float(white_level), _stream())
+    _check(rc, "adaisp_demosaic_rects_ex")
     _wrote(out)
     return out
 

@@ -17,6 +17,21 @@ bool ranges_overlap(const float* a, const float* b, long n) {
     return (a < b + n) && (b < a + n);
 }
 
+int check_demosaic(const uint16_t* raw, const float* out, int B, int H, int W, int pattern, float black, float white) {
+    if (!raw || !out || B <= 0 || H <= 0 || W <= 0) return ADAISP_EINVAL;
+    if (pattern < 0 || pattern > 3 || !(white > black)) return ADAISP_EINVAL;
+    if ((H & 1) || (W & 1) || H < 2 || W < 2 || B > 65535) return ADAISP_ESHAPE;   // whole 2x2 cells
+    return ADAISP_OK;
+}
+
+int check_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, const float* out, int B, int S, int pattern,
+                         float black, float white) {
+    if (!raw || !desc || !out || B < 1 || S < 1) return ADAISP_EINVAL;
+    if (pattern < 0 || pattern > 3 || !(white > black)) return ADAISP_EINVAL;
+    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.z; as adaisp_unprocess_bayer
+    return ADAISP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -66,20 +81,35 @@ int adaisp_pool64_backward(const float* grad_pooled, float* grad_img, int B, int
 
 int adaisp_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black_level,
                     float white_level, void* stream) {
-    if (!raw || !out || B <= 0 || H <= 0 || W <= 0) return ADAISP_EINVAL;
-    if (pattern < 0 || pattern > 3 || !(white_level > black_level)) return ADAISP_EINVAL;
-    if ((H & 1) || (W & 1) || H < 2 || W < 2 || B > 65535) return ADAISP_ESHAPE;   // whole 2x2 cells
+    if (int rc = check_demosaic(raw, out, B, H, W, pattern, black_level, white_level)) return rc;
     return launch_demosaic(raw, out, B, H, W, pattern, black_level, white_level, static_cast<hipStream_t>(stream)) ==
                    hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }
 
 int adaisp_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S, int pattern,
                           float black_level, float white_level, void* stream) {
-    if (!raw || !desc || !out || B < 1 || S < 1) return ADAISP_EINVAL;
-    if (pattern < 0 || pattern > 3 || !(white_level > black_level)) return ADAISP_EINVAL;
-    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.z; as adaisp_unprocess_bayer
+    if (int rc = check_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level)) return rc;
     return launch_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level,
                                  static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+}
+
+int adaisp_demosaic_ex(const uint16_t* raw, float* out, int B, int H, int W, int pattern, int method, float black_level,
+                       float white_level, void* stream) {
+    if (method == ADAISP_DEMOSAIC_BILINEAR) return adaisp_demosaic(raw, out, B, H, W, pattern, black_level, white_level, stream);
+    if (method != ADAISP_DEMOSAIC_MHC) return ADAISP_EINVAL;
+    if (int rc = check_demosaic(raw, out, B, H, W, pattern, black_level, white_level)) return rc;
+    return launch_demosaic_mhc(raw, out, B, H, W, pattern, black_level, white_level, static_cast<hipStream_t>(stream)) ==
+                   hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+}
+
+int adaisp_demosaic_rects_ex(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S, int pattern,
+                             int method, float black_level, float white_level, void* stream) {
+    if (method == ADAISP_DEMOSAIC_BILINEAR)
+        return adaisp_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level, stream);
+    if (method != ADAISP_DEMOSAIC_MHC) return ADAISP_EINVAL;
+    if (int rc = check_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level)) return rc;
+    return launch_demosaic_mhc_rects(raw, desc, out, B, S, pattern, black_level, white_level,
+                                     static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }
 
 int adaisp_process(int op, const float* img, float* out, const float* params, int param_stride, int B, int H, int W,

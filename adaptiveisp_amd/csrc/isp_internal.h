@@ -83,6 +83,10 @@ hipError_t launch_demosaic(const uint16_t* raw, float* out, int B, int H, int W,
                            hipStream_t s);
 hipError_t launch_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
                                  int pattern, float black, float white, hipStream_t s);
+hipError_t launch_demosaic_mhc(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black, float white,
+                               hipStream_t s);
+hipError_t launch_demosaic_mhc_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
+                                     int pattern, float black, float white, hipStream_t s);
 hipError_t launch_backward_params(const float* img, const float* grad_out, const int32_t* ids,
                                   const float* params, int pstride, float* grad_params,
                                   int B, int H, int W, unsigned flags, hipStream_t s);

@@ -109,7 +109,9 @@ class ImageFolderSource:
 
     sensor="bayer" (either data_name, with or without noise, either resize): the same descriptors drive
     adaisp_unprocess_bayer into a reused uint16 device plane (colour filter `cfa`, white level 2**raw_bits - 1,
-    `black_level`, default 2**(raw_bits - 6), 0 below 6 bits) and adaisp_demosaic_rects out of it; the batch keeps its
+    `black_level`, default 2**(raw_bits - 6), 0 below 6 bits) and adaisp_demosaic_rects_ex out of it (`demosaic`:
+    "bilinear", the default, or "mhc", the 5 x 5 gradient-corrected interpolation, which can leave [0, 1] at edges; it has
+    a meaning with sensor="bayer" only and changes nothing before the plane: one seed, one plane); the batch keeps its
     [n,3,S,S] fp32 shape, in [0, 1] over the black..white range. Metadata draws, serials and noise keys are those of
     sensor="rgb": the same seed gives the same sensor parameters in both modes. HIP devices only; an image with a side
     under 2 pixels has no Bayer cell and raises ValueError.
@@ -118,19 +120,21 @@ class ImageFolderSource:
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
                  use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host", sensor="rgb", cfa="RGGB", raw_bits=12,
-                 black_level=None):
-        from ._lib import CFA
+                 black_level=None, demosaic="bilinear"):
+        from ._lib import CFA, DEMOSAIC
         if data_name not in ("lod", "coco"):
             raise ValueError(f"data_name must be 'lod' or 'coco', got {data_name!r}")
         if resize not in ("host", "device"):
             raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
         if sensor not in ("rgb", "bayer"):
             raise ValueError(f"sensor must be 'rgb' or 'bayer', got {sensor!r}")
+        if demosaic not in DEMOSAIC:
+            raise ValueError(f"demosaic must be one of {sorted(DEMOSAIC)}, got {demosaic!r}")
         if not isinstance(cfa, str) or cfa.upper() not in CFA:
             raise ValueError(f"cfa must be one of {sorted(CFA)}, got {cfa!r}")
         if isinstance(raw_bits, bool) or not isinstance(raw_bits, (int, np.integer)) or not 1 <= raw_bits <= 16:
             raise ValueError(f"raw_bits must be an integer in [1, 16], got {raw_bits!r}")
-        self.sensor, self.cfa, self.raw_bits = sensor, cfa.upper(), int(raw_bits)
+        self.sensor, self.cfa, self.raw_bits, self.demosaic = sensor, cfa.upper(), int(raw_bits), demosaic
         self.white_level = 2 ** self.raw_bits - 1
         self.black_level = (2 ** (self.raw_bits - 6) if self.raw_bits >= 6 else 0) if black_level is None else black_level
         if not 0 <= self.black_level < self.white_level or int(self.black_level) != self.black_level:
@@ -139,7 +143,7 @@ class ImageFolderSource:
         self.device = torch.device(device)
         if sensor == "bayer" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(sensor='bayer'): the sensor and its demosaic run on the HIP device only "
-                               "(adaisp_unprocess_bayer, adaisp_demosaic_rects); there is no CPU path")
+                               "(adaisp_unprocess_bayer, adaisp_demosaic_rects_ex); there is no CPU path")
         if data_name == "coco" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(data_name='coco'): the unprocess runs on the HIP device only "
                                "(adaisp_unprocess); there is no CPU path")
@@ -181,6 +185,8 @@ class ImageFolderSource:
     def describe(self):
         kind = "coco (unprocess" + (", noise" if self.add_noise else "") + ")" if self.data_name == "coco" else "lod"
         bayer = f", bayer {self.cfa} {self.raw_bits}-bit black {self.black_level}" if self.sensor == "bayer" else ""
+        if bayer and self.demosaic != "bilinear":
+            bayer += f", {self.demosaic} demosaic"
         return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "") + bayer
 
     # ------------------------------------------------------------------------------------------------------ order
@@ -332,7 +338,7 @@ class ImageFolderSource:
                 self._plane = torch.empty((B, S, S), dtype=torch.uint16, device=self.device)
             levels = dict(pattern=self.cfa, black_level=self.black_level, white_level=self.white_level)
             raw = _lib.unprocess_bayer(pixels, records, S, seed=self.seed, flags=flags, out=self._plane[:B], **levels)
-            return _lib.demosaic_rects(raw, records, **levels)
+            return _lib.demosaic_rects(raw, records, method=self.demosaic, **levels)
 
     def _resize_on_device(self, lay, total):
         """The two adaisp_resize_u8 calls of a staged batch (see _resize_plan), on the current stream."""

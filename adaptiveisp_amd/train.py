@@ -381,13 +381,13 @@ class _GraphIteration:
 def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epochs=800, save_dir=None, sync_bn=False,
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
                   add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host",
-                  sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None):
+                  sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear"):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
     reference's unprocess options; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
     where the resample to the training size runs; `sensor` "bayer": through the simulated `cfa` / `raw_bits` /
-    `black_level` sensor and its demosaic); None: SyntheticSource."""
+    `black_level` sensor and its `demosaic`, "bilinear" or "mhc"); None: SyntheticSource."""
     import random
 
     from .agent import Agent
@@ -423,7 +423,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
         source = ImageFolderSource(data, H, device, data_name=data_name, add_noise=add_noise,
                                    brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
                                    seed=seed, rank=rank, world=world, workers=workers, resize=resize,
-                                   sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level)
+                                   sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level, demosaic=demosaic)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -461,7 +461,9 @@ def build_parser():
                          "(a HIP kernel; use it for photo-sized datasets, where the host resample cannot keep up)")
     ap.add_argument("--sensor", default="rgb", choices=("rgb", "bayer"),
                     help="rgb: the converted image as it is; bayer: through a simulated Bayer sensor (one colour per pixel, "
-                         "noise on that sample, quantised) and its bilinear demosaic, both HIP kernels")
+                         "noise on that sample, quantised) and its demosaic (--demosaic), both HIP kernels")
+    ap.add_argument("--demosaic", default="bilinear", choices=("bilinear", "mhc"),
+                    help="bayer: 3 x 3 bilinear interpolation, or mhc, the 5 x 5 gradient-corrected one (Malvar-He-Cutler)")
     ap.add_argument("--cfa", default="RGGB", choices=("RGGB", "GRBG", "GBRG", "BGGR"), help="bayer: colour filter array")
     ap.add_argument("--raw-bits", type=int, default=12, help="bayer: sample depth (white level 2^bits - 1)")
     ap.add_argument("--black-level", type=int, default=None, help="bayer: black level (default 2^(bits - 6))")
@@ -509,7 +511,7 @@ def main(argv=None):
                            sync_bn=a.sync_bn, detector_ckpt=a.detector_ckpt, isp_ckpt=a.isp_ckpt, seed=a.seed, tune_cache=cache,
                            data=a.data, data_name=a.data_name, add_noise=a.add_noise, brightness_range=a.bri_range,
                            noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers, resize=a.resize,
-                           sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level)
+                           sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic)
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

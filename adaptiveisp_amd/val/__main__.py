@@ -117,7 +117,9 @@ def build_parser():
                          "(a HIP kernel; use it for photo-sized datasets, where the host resample cannot keep up)")
     ap.add_argument("--sensor", default="rgb", choices=("rgb", "bayer"),
                     help="rgb: the converted image as it is; bayer: through a simulated Bayer sensor (one colour per pixel, "
-                         "noise on that sample, quantised) and its bilinear demosaic, both HIP kernels")
+                         "noise on that sample, quantised) and its demosaic (--demosaic), both HIP kernels")
+    ap.add_argument("--demosaic", default="bilinear", choices=("bilinear", "mhc"),
+                    help="bayer: 3 x 3 bilinear interpolation, or mhc, the 5 x 5 gradient-corrected one (Malvar-He-Cutler)")
     ap.add_argument("--cfa", default="RGGB", choices=("RGGB", "GRBG", "GBRG", "BGGR"), help="bayer: colour filter array")
     ap.add_argument("--raw-bits", type=int, default=12, help="bayer: sample depth (white level 2^bits - 1)")
     ap.add_argument("--black-level", type=int, default=None, help="bayer: black level (default 2^(bits - 6))")
@@ -228,7 +230,7 @@ def main(argv=None):
     src = ImageFolderSource(source, a.img_size, dev, data_name=a.data_name, add_noise=a.add_noise,
                             brightness_range=a.bri_range, noise_level=a.noise_level, use_linear=a.use_linear,
                             seed=a.seed, workers=a.workers, resize=a.resize, sensor=a.sensor, cfa=a.cfa,
-                            raw_bits=a.raw_bits, black_level=a.black_level)
+                            raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic)
     n_files = len(src)
     engines = {}
     for b in {min(a.batch_size, n_files), n_files % a.batch_size or a.batch_size}:

@@ -206,6 +206,37 @@ int adaisp_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc
                           float black_level, float white_level, void* stream);
 
 /*
+ * The two demosaics with a choice of interpolation. method ADAISP_DEMOSAIC_BILINEAR launches the kernels of adaisp_demosaic
+ * / adaisp_demosaic_rects (bit-identical to them); ADAISP_DEMOSAIC_MHC is the 5 x 5 gradient-corrected linear interpolation
+ * of Malvar, He and Cutler (2004), under the same contracts: raw, out, pattern, H and W even (whole frame); descriptors,
+ * phase and mirror at the rectangle, exactly 0 outside it, h < 2 / w < 2 / a placement that does not fit all zero, any
+ * S >= 1 (rectangles). It works on the un-normalised samples t = float(raw) - black_level. With C the centre sample, N S W E
+ * the neighbours at distance 1, N2 S2 W2 E2 those at distance 2 and D = NW + NE + SW + SE:
+ *     the site's own colour                                 acc = 8 C
+ *     G at an R or B site                                   acc = 4 C + 2 (N + S + W + E) - (N2 + S2 + W2 + E2)
+ *     R at a B site, B at an R site                         acc = 6 C + 2 D - 1.5 (N2 + S2 + W2 + E2)
+ *     R or B at a G site, the wanted colour lying W / E     acc = 5 C + 4 (W + E) - D - (W2 + E2) + 0.5 (N2 + S2)
+ *     R or B at a G site, the wanted colour lying N / S     acc = 5 C + 4 (N + S) - D - (N2 + S2) + 0.5 (W2 + E2)
+ *     out = (acc * 0.125f) * (1.0f / (white_level - black_level))
+ * With a whole-number black_level in [0, 65535] (so |raw - black_level| <= 65535) every term is a multiple of 0.5 and 2
+ * |acc| <= 40 * 65535 < 2^24: acc is exact in fp32 whatever the order, the last multiply is the only rounding, and a sampled
+ * colour equals the bilinear (raw - black) * inv_range bit for bit. Borders mirror without repeating the edge sample, folded
+ * as often as needed (period 2n - 2, numpy's "reflect": -1 -> 1, -2 -> 2, and on a 2-pixel side -2 -> 0), which keeps the
+ * Bayer phase on any side >= 2. Nothing is clamped, as in the bilinear kernels: the filters over- and undershoot at edges
+ * (values outside [0,1]) and the filter stack has its own clips.
+ * Arguments, limits and error codes as adaisp_demosaic / adaisp_demosaic_rects; an unknown method is ADAISP_EINVAL.
+ * Other levels are accepted as they are by the bilinear entries (only white_level > black_level is checked): the filters
+ * are the same, but a fractional or out-of-range black_level gives up the bit-for-bit guarantee, not the result.
+ * No allocation, no host synchronisation: capturable in a hipGraph.
+ */
+#define ADAISP_DEMOSAIC_BILINEAR 0
+#define ADAISP_DEMOSAIC_MHC      1
+int adaisp_demosaic_ex(const uint16_t* raw, float* out, int B, int H, int W, int pattern, int method,
+                       float black_level, float white_level, void* stream);
+int adaisp_demosaic_rects_ex(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
+                             int pattern, int method, float black_level, float white_level, void* stream);
+
+/*
  * Replay-pool resampling on the device: the pixel work of `load_image` (dataloaders.py:735-750: longer side to S, area
  * filter when shrinking, bilinear otherwise) and of `letterbox`'s resize to the un-padded size (augmentations.py:111-141),
  * uint8 HWC BGR -> uint8 HWC BGR, every image with its own sizes, mode and byte offsets. Each mode reproduces the
