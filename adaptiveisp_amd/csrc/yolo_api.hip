@@ -722,6 +722,23 @@ int adayolo_match(const adayolo_match_args* a, void* stream) {
     return code(launch_match(*a, static_cast<hipStream_t>(stream)));
 }
 
+size_t adayolo_nms_batch_workspace_bytes(int B, int N, int nc, int cap, int max_nms, int max_det) {
+    (void)N; (void)nc; (void)max_nms;                // the workspace holds cap keys and max_det staged rows per image
+    return nms_batch_layout(B, cap, max_det).bytes;
+}
+
+int adayolo_nms_batch(const adayolo_nms_batch_args* a, void* stream) {
+    if (!a || !a->pred || !a->workspace || !a->det || !a->det_offset || !a->status) return ADAYOLO_EINVAL;
+    if (a->B < 0 || a->N < 0 || a->nc < 1 || (long)a->N * a->nc > 0x7fffffffL || (long)a->B * a->N > 0x7fffffffL) return ADAYOLO_ESHAPE;
+    if (a->pred_row_stride < 5 + a->nc) return ADAYOLO_ESHAPE;
+    if (!(a->conf_thres >= 0.0f && a->conf_thres <= 1.0f) || !(a->iou_thres >= 0.0f && a->iou_thres <= 1.0f)) return ADAYOLO_ESHAPE;
+    if (a->max_det < 1 || a->max_det > kNmsBatchMaxDet || a->max_nms < 1 || a->cap < 1 || a->cap > (1 << 30)) return ADAYOLO_ESHAPE;
+    if (a->flags & ~(ADAYOLO_NMS_MULTI_LABEL | ADAYOLO_NMS_AGNOSTIC)) return ADAYOLO_ESHAPE;
+    if (a->workspace_bytes < nms_batch_layout(a->B, a->cap, a->max_det).bytes) return ADAYOLO_ESHAPE;
+    if (a->B == 0 || a->N == 0) return ADAYOLO_OK;
+    return code(launch_nms_batch(*a, static_cast<hipStream_t>(stream)));
+}
+
 static int detloss_check(const adayolo_loss_args* a, bool bwd) {
     if (!a || a->nl < 1 || a->nl > 4 || a->B < 1 || a->B > 65535 || a->na < 1 || a->nc < 1 || a->no != a->nc + 5 || !a->loss || !a->ticket)
         return ADAYOLO_EINVAL;

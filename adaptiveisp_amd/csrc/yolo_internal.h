@@ -116,5 +116,10 @@ hipError_t launch_detloss_bwd(const adayolo_loss_args& a, hipStream_t s);
 hipError_t launch_nms(const float* boxes, int n, float thr, int max_det, unsigned long long* mask_ws, int* keep,
                       int* num_keep, hipStream_t s);
 hipError_t launch_match(const adayolo_match_args& a, hipStream_t s);          // yolo_match.hip
+// whole-batch NMS (yolo_nms_batch.hip): the workspace's layout is a function of (B, cap, max_det) alone; bytes == 0: not served
+constexpr int kNmsBatchMaxDet = 2048;                                          // the kept list lives in LDS
+struct NmsBatchLayout { int P; size_t off_count, off_keep, off_keys, off_stage, bytes; };   // P: key slots per image (cap rounded up to a power of two)
+NmsBatchLayout nms_batch_layout(int B, int cap, int max_det);
+hipError_t launch_nms_batch(const adayolo_nms_batch_args& a, hipStream_t s);
 
 }  // namespace adayolo

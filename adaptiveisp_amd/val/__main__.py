@@ -107,6 +107,9 @@ def build_parser():
     ap.add_argument("--graph", action="store_true", help="replay each batch's ISP episode + detector as one hipGraph")
     ap.add_argument("--match", default="host", choices=("host", "device"),
                     help="where detections are matched to labels: host (torch, per image) or device (one HIP launch per batch)")
+    ap.add_argument("--nms", default="host", choices=("host", "device"),
+                    help="where NMS runs: host (per image, with a host read each) or device (adayolo_nms_batch: the whole batch "
+                         "in four launches, rows left on the device for the matching); device implies --match device")
     ap.add_argument("--confusion", action="store_true",
                     help="confusion_matrix.csv (conf 0.25, IoU 0.45); with --verbose also its per-class counts")
     ap.add_argument("--seed", type=int, default=0)
@@ -133,6 +136,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.batch_size < 1 or a.steps < 1:
         ap.error("--batch-size and --steps must be positive")
+    if a.nms == "device" and a.match != "device":
+        # the device NMS leaves its rows where adayolo_match reads them: there is no host matching behind it
+        print("--nms device: matching runs on the device too (--match device)")
+        a.match = "device"
     if a.pipeline is not None:
         try:
             a.pipeline = [int(x) for x in a.pipeline.split(",")]
@@ -268,7 +275,7 @@ def main(argv=None):
                        pipeline=a.pipeline, records_path=os.path.join(save_dir, "records.txt"), nc=nc,
                        param_dir=os.path.join(save_dir, "param_results") if a.save_param else None, graph=a.graph,
                        image_dir=image_dir, image_writer=writer,
-                       on_image=on_image if (a.save_txt or a.save_json) else None, match=a.match,
+                       on_image=on_image if (a.save_txt or a.save_json) else None, match=a.match, nms=a.nms,
                        confusion=True if a.confusion else None)
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0

@@ -12,10 +12,15 @@ from .. import _lib
 from ..util import STATE_STOPPED_DIM
 from .boxes import scale_boxes, xywh2xyxy
 from .metrics import ConfusionMatrix, ap_per_class, match_batch, process_batch
-from .nms import non_max_suppression
+from .nms import MAX_NMS, non_max_suppression, non_max_suppression_device
 
 
 _SIDE = {}
+
+
+def _yolo_lib():
+    from ..yolo import _lib as yolo_lib
+    return yolo_lib
 
 
 def _side_stream(dev):
@@ -117,7 +122,7 @@ class _EpisodeGraph:
 
 def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False,
              pipeline=None, records_path=None, nc=80, nms_fn=None, param_dir=None, details=None, graph=False,
-             image_dir=None, image_writer=None, on_image=None, match="host", confusion=None):
+             image_dir=None, image_writer=None, on_image=None, match="host", confusion=None, nms="host"):
     """Returns dict(mp, mr, map50, map75, map, seen, nt, ap_class, ap, records). `detector(x)` -> [B, N, 5+nc]
     decoded predictions (YoloEngine or the module tree in eval mode). `pipeline`: optional list of forced filter ids
     per step (val_adaptiveisp.py:292, --pipeline). `param_dir`: write one JSON per batch (named after its first image) with
@@ -142,7 +147,14 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
     from the default mode's in their last bit (never more: tests/test_gpu_match.py), and a detection whose IoU sits within that
     of a level can change its `correct` entry there. The device mode is the one that agrees with a CPU run of the loop.
     `confusion`: True (a ConfusionMatrix(nc) of the defaults) or a ConfusionMatrix to add to — filled per image on the host,
-    or inside the same launch with match="device"; the result then gains `confusion`, its integer [nc+1, nc+1] matrix."""
+    or inside the same launch with match="device"; the result then gains `confusion`, its integer [nc+1, nc+1] matrix.
+    `nms`: "host" (the default: val.non_max_suppression — per image an argsort, two NMS launches and a host read) or "device"
+    (HIP device and match="device" only, no `nms_fn`): `adayolo_nms_batch` takes the predictions of the whole batch to kept rows
+    and row offsets on the device (val.non_max_suppression_device) and `adayolo_match` reads them where they are — no list of
+    per-image tensors, no concatenation, no re-upload of counts. ONE host read per batch between the forward and the `stats`
+    append: the offsets and the per-image status words together, through pinned memory. The rows equal the host function's on
+    CPU tensors bit for bit. A batch in which an image has more candidates than the kernel's slots (its status says so) goes
+    through the host function instead; the result's `nms_fallbacks` counts such batches (0 with nms="host")."""
     import collections
     import json
     from ..util import get_initial_states, get_noise, to_device_async
@@ -151,6 +163,15 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
         raise ValueError(f"match={match!r}: expected 'host' or 'device'")
     if match == "device" and dev.type != "cuda":
         raise ValueError(f"match='device' runs the adayolo_match kernel and needs a HIP device; the agent is on '{dev}'")
+    if nms not in ("host", "device"):
+        raise ValueError(f"nms={nms!r}: expected 'host' or 'device'")
+    if nms == "device" and dev.type != "cuda":
+        raise ValueError(f"nms='device' runs the adayolo_nms_batch kernels and needs a HIP device; the agent is on '{dev}'")
+    if nms == "device" and match != "device":
+        raise ValueError("nms='device' leaves its rows on the device for adayolo_match: it needs match='device'")
+    if nms == "device" and nms_fn is not None:
+        raise ValueError("nms='device' runs its own NMS: `nms_fn` belongs to nms='host'")
+    nms_state = dict(fallbacks=0, ws=None, pin={})
     cm = ConfusionMatrix(nc) if confusion is True else (confusion or None)
     iouv = torch.linspace(0.5, 0.95, 10, device=dev)
     niou = iouv.numel()
@@ -238,11 +259,20 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
             for i, step_ids in enumerate(ids):
                 row[i] = str(step_ids[b])
             records.append((os.path.split(str(paths[b]))[1], row))
-        preds = non_max_suppression(preds, conf_thres, iou_thres, multi_label=True, agnostic=single_cls,
-                                    max_det=max_det, nms_fn=nms_fn)
-        if match == "device":
-            back_device(preds, im, targets, paths, shapes, retouch)
+        if isinstance(preds, (list, tuple)):
+            preds = preds[0]
+        rows = None
+        if nms == "device":
+            rows = nms_device(preds)                                   # None: an image overflowed, the host function below
+        if rows is not None:
+            back_device(None, im, targets, paths, shapes, retouch, rows)
             preds = []
+        else:
+            preds = non_max_suppression(preds, conf_thres, iou_thres, multi_label=True, agnostic=single_cls,
+                                        max_det=max_det, nms_fn=nms_fn)
+            if match == "device":
+                back_device(preds, im, targets, paths, shapes, retouch)
+                preds = []
         for si, pred in enumerate(preds):
             labels = targets[targets[:, 0] == si, 1:]
             nl, npr = labels.shape[0], pred.shape[0]
@@ -277,20 +307,54 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
         if slot is not None:
             _EpisodeGraph.release(slot)
 
-    def back_device(preds, im, targets, paths, shapes, retouch):
-        """The matching of one batch as ONE launch (match="device"): what the loop over the images in `back` does."""
+    def nms_device(preds):
+        """nms="device": (det rows of the batch [K, 6], per-image counts, det_offset on the device), or None when an image
+        had more candidates than slots. The batch's one host read: offsets and status words in one pinned copy."""
+        nb = preds.shape[0]
+        if not (preds.is_cuda and preds.dtype == torch.float32):
+            preds = preds.to(dev, torch.float32)
+        nc_, cap = preds.shape[2] - 5, None
+        need = _yolo_lib().load().adayolo_nms_batch_workspace_bytes(nb, preds.shape[1], nc_, max(1, min(preds.shape[1] * nc_, 131072)),
+                                                                     MAX_NMS, max_det)
+        if nms_state["ws"] is None or nms_state["ws"].numel() < need:
+            nms_state["ws"] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)    # this stream's, batch after batch
+        det, det_offset, status = non_max_suppression_device(preds, conf_thres, iou_thres, agnostic=single_cls, multi_label=True,
+                                                             max_det=max_det, cap=cap, workspace=nms_state["ws"])
+        pin = nms_state["pin"].get(nb)
+        if pin is None:
+            pin = nms_state["pin"][nb] = torch.empty(2 * nb + 1, dtype=torch.int32, pin_memory=True)
+        pin.copy_(torch.cat((det_offset, status)), non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        words = pin.tolist()
+        if any(words[nb + 1:]):
+            nms_state["fallbacks"] += 1
+            return None
+        counts = [words[i + 1] - words[i] for i in range(nb)]
+        return det[:words[nb]], counts, det_offset
+
+    def back_device(preds, im, targets, paths, shapes, retouch, rows=None):
+        """The matching of one batch as ONE launch (match="device"): what the loop over the images in `back` does. `rows`: the
+        batch's rows as nms_device left them on the device (then `preds` is not used)."""
         nonlocal seen
-        nb = len(preds)
-        counts = [int(p.shape[0]) for p in preds]
+        if rows is None:
+            nb = len(preds)
+            counts = [int(p.shape[0]) for p in preds]
+            det = torch.cat(preds, 0) if nb > 1 else preds[0]
+            det_offset = None
+        else:
+            det, counts, det_offset = rows
+            nb = len(counts)
         if details is not None:
-            for si, pred in enumerate(preds):
-                details.append(dict(path=str(paths[si]), retouch=retouch[si].detach().cpu(), pred=pred.detach().cpu().clone(),
+            det_h, start = det.detach().cpu(), 0
+            for si, k in enumerate(counts):
+                details.append(dict(path=str(paths[si]), retouch=retouch[si].detach().cpu(), pred=det_h[start:start + k].clone(),
                                     correct=None))
+                start += k
         seen += nb
-        det = torch.cat(preds, 0) if nb > 1 else preds[0]
         if single_cls:
             det[:, 5] = 0
-        # per image (gain, pad_x, pad_y, h0, w0) and the row offsets: one pinned buffer, one asynchronous copy
+        # per image (gain, pad_x, pad_y, h0, w0) and the row offsets: one pinned buffer, one asynchronous copy (the offsets of
+        # nms="device" are on the device already: they are not sent again)
         host = np.zeros(nb * 5 + nb + 1, np.int32)
         geom = host[:nb * 5].view(np.float32).reshape(nb, 5)
         h1, w1 = im.shape[2:]
@@ -304,7 +368,7 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
             geom[si] = (gain, pad[0], pad[1], h0, w0)
         host[nb * 5 + 1:] = np.cumsum(counts)
         up = to_device_async(host, dev)
-        args = (det, up[nb * 5:], targets, up[:nb * 5].view(torch.float32).view(nb, 5), iouv)
+        args = (det, up[nb * 5:] if det_offset is None else det_offset, targets, up[:nb * 5].view(torch.float32).view(nb, 5), iouv)
         predn, correct = cm.process_batch_device(*args) if cm is not None else match_batch(*args, nc)
         correct = correct.bool()
         if det.shape[0] or targets.shape[0]:
@@ -356,6 +420,7 @@ def run_eval(agent, detector, batches, cfg, steps=5, conf_thres=0.001, iou_thres
     res["nt"] = np.bincount(stats[3].astype(int), minlength=nc) if len(stats) else np.zeros(nc, int)
     if cm is not None:
         res["confusion"] = cm.matrix
+    res["nms_fallbacks"] = nms_state["fallbacks"]
     if records_path:
         with open(records_path, "w") as f:                         # val_adaptiveisp.py:269-322 "records.txt"
             f.write(",".join(filter_names) + "\n")

@@ -117,3 +117,26 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
         kept = nms_fn(seg[:, :4] + offset, seg[:, 4], iou_thres)[:max_det]
         output.append(seg[kept])
     return output
+
+
+def non_max_suppression_device(prediction, conf_thres=0.25, iou_thres=0.45, agnostic=False, multi_label=False, max_det=300,
+                               cap=None, workspace=None, out=None):
+    """non_max_suppression for the whole batch on the device (csrc/yolo_nms_batch.hip through `adayolo_nms_batch`): prediction
+    fp32 [B, N, 5+nc] on a HIP device -> (det [B*max_det, 6], det_offset int32 [B+1], status int32 [B]), all on the device and
+    without a host read: image b's rows (xyxy, conf, cls; what the host function returns for it, bit for bit) are
+    det[det_offset[b]:det_offset[b+1]] — the inputs of `adayolo_match`. `cap`: candidate slots per image (default
+    min(N*nc, 131072)); status[b] != 0: image b had more candidates and its rows are not to be used (run_eval sends such a
+    batch through the host function). `labels`, `classes` and mask coefficients stay with the host function."""
+    from ..yolo import _lib
+    if not 0 <= conf_thres <= 1:
+        raise ValueError(f"confidence threshold {conf_thres} outside [0, 1]")
+    if not 0 <= iou_thres <= 1:
+        raise ValueError(f"IoU threshold {iou_thres} outside [0, 1]")
+    if isinstance(prediction, (list, tuple)):
+        prediction = prediction[0]
+    if not (isinstance(prediction, torch.Tensor) and prediction.is_cuda):
+        raise _lib.AdayoloError("non_max_suppression_device needs a HIP device tensor: there is no CPU path")
+    if cap is None:
+        cap = max(1, min(prediction.shape[1] * (prediction.shape[2] - 5), 131072))
+    return _lib.nms_batch(prediction, conf_thres, iou_thres, max_det, MAX_NMS, cap, multi_label, agnostic, workspace=workspace,
+                          out=out)

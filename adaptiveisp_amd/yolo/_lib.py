@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("ADAYOLO_LIB") or os.path.join(_HERE, "csrc", "libadayolo.so")
 ABI_VERSION = 10
 ACT_NONE, ACT_SILU = 0, 1
-EXPORTS = ("adayolo_conv_fwd", "adayolo_conv_fwd_variant", "adayolo_conv_fused1x1_fwd", "adayolo_conv1x1_stream_fwd", "adayolo_bottleneck256_fwd", "adayolo_bottleneck_ws_fwd", "adayolo_conv_keep_fwd", "adayolo_conv_splitk_fwd", "adayolo_conv_dsilu_fwd", "adayolo_conv_s2grad_fwd", "adayolo_conv_splitk_workspace_bytes", "adayolo_conv_chain_workspace_bytes", "adayolo_conv_chain_prepare", "adayolo_conv_chain_fwd", "adayolo_conv_chain_status", "adayolo_conv_chain_poll", "adayolo_conv_chain_tables", "adayolo_stem_fwd", "adayolo_upsample2x", "adayolo_detect_decode", "adayolo_nms", "adayolo_nms_workspace_bytes", "adayolo_match", "adayolo_stem_fwd_act", "adayolo_stem_keep_fwd", "adayolo_stem_down_fwd", "adayolo_letterbox_pack", "adayolo_silu_fwd", "adayolo_silu_bwd",
+EXPORTS = ("adayolo_conv_fwd", "adayolo_conv_fwd_variant", "adayolo_conv_fused1x1_fwd", "adayolo_conv1x1_stream_fwd", "adayolo_bottleneck256_fwd", "adayolo_bottleneck_ws_fwd", "adayolo_conv_keep_fwd", "adayolo_conv_splitk_fwd", "adayolo_conv_dsilu_fwd", "adayolo_conv_s2grad_fwd", "adayolo_conv_splitk_workspace_bytes", "adayolo_conv_chain_workspace_bytes", "adayolo_conv_chain_prepare", "adayolo_conv_chain_fwd", "adayolo_conv_chain_status", "adayolo_conv_chain_poll", "adayolo_conv_chain_tables", "adayolo_stem_fwd", "adayolo_upsample2x", "adayolo_detect_decode", "adayolo_nms", "adayolo_nms_workspace_bytes", "adayolo_match", "adayolo_nms_batch", "adayolo_nms_batch_workspace_bytes", "adayolo_stem_fwd_act", "adayolo_stem_keep_fwd", "adayolo_stem_down_fwd", "adayolo_letterbox_pack", "adayolo_silu_fwd", "adayolo_silu_bwd",
            "adayolo_zero_insert2x", "adayolo_upsample2x_bwd", "adayolo_image_grad", "adayolo_detloss_fwd", "adayolo_detloss_bwd",
            "adayolo_strerror", "adayolo_set_mfma_shape", "adayolo_get_mfma_shape",
            "adayolo_abi_version")
@@ -53,6 +53,17 @@ class MatchArgs(ctypes.Structure):                 # adayolo_match_args
 
 
 MATCH_NATIVE = 1
+
+
+class NmsBatchArgs(ctypes.Structure):              # adayolo_nms_batch_args
+    _fields_ = [("pred", ctypes.c_void_p), ("pred_row_stride", ctypes.c_int32), ("B", ctypes.c_int32), ("N", ctypes.c_int32),
+                ("nc", ctypes.c_int32), ("conf_thres", ctypes.c_float), ("iou_thres", ctypes.c_float),
+                ("max_det", ctypes.c_int32), ("max_nms", ctypes.c_int32), ("cap", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("det", ctypes.c_void_p),
+                ("det_offset", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+NMS_MULTI_LABEL, NMS_AGNOSTIC, NMS_OVERFLOW = 1, 2, 1
 
 
 def load():
@@ -126,6 +137,10 @@ def load():
     L.adayolo_nms_workspace_bytes.restype = ctypes.c_size_t
     L.adayolo_match.argtypes = [ctypes.POINTER(MatchArgs), vp]
     L.adayolo_match.restype = ci
+    L.adayolo_nms_batch.argtypes = [ctypes.POINTER(NmsBatchArgs), vp]
+    L.adayolo_nms_batch.restype = ci
+    L.adayolo_nms_batch_workspace_bytes.argtypes = [ci] * 6
+    L.adayolo_nms_batch_workspace_bytes.restype = ctypes.c_size_t
     L.adayolo_set_mfma_shape.argtypes = [ci, ci]
     L.adayolo_set_mfma_shape.restype = ci
     L.adayolo_get_mfma_shape.argtypes = [ci]
@@ -192,3 +207,46 @@ def match(det, det_offset, targets, geom, iouv, nc, native=False, confusion=None
         rc = load().adayolo_match(ctypes.byref(a), stream_ptr())
     check(rc, "adayolo_match")
     return predn[:K], correct[:K]
+
+
+def nms_batch(pred, conf_thres, iou_thres, max_det, max_nms, cap, multi_label, agnostic, workspace=None, out=None):
+    """adayolo_nms_batch (include/adayolo.h) on the current stream: pred fp32 [B, N, 5+nc] on a HIP device, rows contiguous (a
+    view into a wider buffer is taken as it is: its row stride is handed over) -> (det fp32 [B*max_det, 6], det_offset int32
+    [B+1], status int32 [B]); image b's kept rows are det[det_offset[b]:det_offset[b+1]], the rows behind det_offset[B] are
+    uninitialised. `workspace`: a uint8 device tensor of at least adayolo_nms_batch_workspace_bytes(...) bytes (default: one
+    is allocated); `out`: (det, det_offset, status) to write into, as a captured graph needs them. Four launches, no host
+    synchronisation."""
+    what = "adayolo_nms_batch"
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda):
+        raise AdayoloError(f"{what}: pred must be a HIP device tensor: there is no CPU path")
+    if pred.dtype != torch.float32 or pred.ndim != 3 or pred.shape[2] < 6:
+        raise AdayoloError(f"{what}: pred must be fp32 [B, N, 5+nc] with nc >= 1, got {pred.dtype} {tuple(pred.shape)}")
+    B, N, C = pred.shape
+    if B and N and not (pred.stride(2) == 1 and pred.stride(1) >= C and pred.stride(0) == N * pred.stride(1)):
+        pred = pred.contiguous()
+    dev, stride = pred.device, (pred.stride(1) if B and N else C)
+    L = load()
+    need = L.adayolo_nms_batch_workspace_bytes(B, N, C - 5, int(cap), int(max_nms), int(max_det))
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise AdayoloError(f"{what}: workspace must be a contiguous uint8 tensor on pred's device")
+    if out is None:
+        # (zeroed: with B == 0 or N == 0 the entry launches nothing and writes nothing)
+        out = (torch.empty((max(B * int(max_det), 1), 6), dtype=torch.float32, device=dev),
+               torch.zeros(B + 1, dtype=torch.int32, device=dev), torch.zeros(max(B, 1), dtype=torch.int32, device=dev))
+    det, det_offset, status = out
+    for t, dt, n, name in ((det, torch.float32, B * int(max_det) * 6, "det"), (det_offset, torch.int32, B + 1, "det_offset"),
+                           (status, torch.int32, B, "status")):
+        if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() < n:
+            raise AdayoloError(f"{what}: {name} must be a contiguous {dt} tensor of at least {n} elements on pred's device")
+    a = NmsBatchArgs()
+    a.pred, a.pred_row_stride, a.B, a.N, a.nc = pred.data_ptr() or det.data_ptr(), stride, B, N, C - 5
+    a.conf_thres, a.iou_thres, a.max_det, a.max_nms, a.cap = float(conf_thres), float(iou_thres), int(max_det), int(max_nms), int(cap)
+    a.flags = (NMS_MULTI_LABEL if multi_label else 0) | (NMS_AGNOSTIC if agnostic else 0)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    a.det, a.det_offset, a.status = det.data_ptr(), det_offset.data_ptr(), status.data_ptr()
+    with torch.cuda.device(dev):
+        rc = L.adayolo_nms_batch(ctypes.byref(a), stream_ptr())
+    check(rc, what)
+    return det, det_offset, status[:B]

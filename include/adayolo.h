@@ -383,6 +383,56 @@ typedef struct adayolo_match_args {
 int adayolo_match(const adayolo_match_args* args, void* stream);
 
 /*
+ * non_max_suppression of the eval loop for a whole batch (csrc/yolo_nms_batch.hip): what val/nms.py::non_max_suppression does
+ * per image on the host (yolov3/utils/general.py:856-966), from the detector's decoded predictions to the inputs of
+ * adayolo_match. FOUR launches whatever B, the data and the candidate counts are; no host synchronisation, no allocation, no
+ * copy: the call can be captured into a graph on one stream. (ABI 10 still: the entry is an addition, nothing that existed
+ * changes; a caller that must know looks the symbol up.)
+ *   candidates  row r of image b (xywh, obj, cls[nc] at pred + (b*N + r)*pred_row_stride) with obj > conf_thres; with
+ *               ADAYOLO_NMS_MULTI_LABEL and nc > 1 one candidate per class c with cls[c]*obj > conf_thres, otherwise the class
+ *               with the highest product (the lowest index among equal products) if that product is > conf_thres. All
+ *               comparisons in fp32. score = cls[c]*obj.
+ *   order       per image by descending score, then ascending r*nc + c (a stable sort of the candidates in row-major order);
+ *               the first max_nms enter the NMS.
+ *   NMS         greedy in that order: box = (x - w/2, y - h/2, x + w/2, y + h/2), plus c*7680 on all four coordinates unless
+ *               ADAYOLO_NMS_AGNOSTIC; a box is kept unless an earlier KEPT box has IoU > iou_thres with it (IoU = inter /
+ *               (area_a + area_b - inter), extents clamped at 0, no contraction: adayolo_nms's arithmetic); at most max_det.
+ *   outputs     det rows [x1, y1, x2, y2, score, c] (boxes WITHOUT the class offset), in score order, image b at rows
+ *               det_offset[b] .. det_offset[b+1] (det_offset[0] = 0); rows past det_offset[B] are not written. Every output
+ *               equals what the host function gives on CPU tensors, bit for bit.
+ *   cap         candidate slots per image. status[b] = 0, or ADAYOLO_NMS_OVERFLOW when image b has more candidates than cap:
+ *               nothing is written out of bounds and the image gets NO rows (det_offset[b+1] == det_offset[b]: which cap of its
+ *               candidates were stored depends on timing, so they are not sorted at all); the other images are unaffected.
+ * workspace: device memory of adayolo_nms_batch_workspace_bytes(B, N, nc, cap, max_nms, max_det) bytes (linear in B*cap:
+ * 8 bytes per slot, cap rounded up to a power of two, plus 24 bytes per image and max_det row), 8-byte aligned, contents
+ * irrelevant before and after a call. The function depends on its arguments alone, is non-decreasing in each, and is 0 for
+ * arguments the call would reject.
+ * ADAYOLO_EINVAL: a null pointer (args, pred, workspace, det, det_offset, status). ADAYOLO_ESHAPE: nc < 1, N*nc or B*N beyond
+ * 31 bits, a negative count, pred_row_stride < 5 + nc, a threshold outside [0, 1], max_det < 1 or > 2048 (the kept list lives
+ * in LDS), max_nms < 1, cap < 1 or > 2^30, unknown flags, workspace_bytes too small. All checked before any launch.
+ * B == 0 or N == 0 returns 0 WITHOUT a launch: no output is written, det_offset and status included — a caller that reads
+ * them in that case zeroes them itself (yolo/_lib.py: nms_batch does).
+ */
+#define ADAYOLO_NMS_MULTI_LABEL 1
+#define ADAYOLO_NMS_AGNOSTIC    2
+#define ADAYOLO_NMS_OVERFLOW    1   /* a status value */
+typedef struct adayolo_nms_batch_args {
+    const float* pred;             /* [B][N] rows of 5 + nc floats: x, y, w, h, obj, cls... */
+    int32_t      pred_row_stride;  /* floats between consecutive rows (>= 5 + nc; image b starts at row b*N) */
+    int32_t      B, N, nc;
+    float        conf_thres, iou_thres;
+    int32_t      max_det, max_nms, cap;
+    int32_t      flags;            /* ADAYOLO_NMS_MULTI_LABEL | ADAYOLO_NMS_AGNOSTIC */
+    void*        workspace;
+    size_t       workspace_bytes;
+    float*       det;              /* [B*max_det][6] out */
+    int32_t*     det_offset;       /* [B+1] out */
+    int32_t*     status;           /* [B] out */
+} adayolo_nms_batch_args;
+size_t adayolo_nms_batch_workspace_bytes(int B, int N, int nc, int cap, int max_nms, int max_det);
+int adayolo_nms_batch(const adayolo_nms_batch_args* args, void* stream);
+
+/*
  * Per-image detection loss of the RL reward on the RAW head maps, with its gradient (training path). Replaces the
  * caller-side Python of train.py:175-197 — `ComputeLossBatch` called once per sample with the image index of its targets
  * set to 0 — i.e. ComputeLoss.__call__ (yolov3/utils/loss.py:115-170 / :262-318) and bbox_iou(CIoU=True)

@@ -2,8 +2,9 @@
 """Per-image time of the evaluation loop at BASELINE config 3's shape (batch 1, 512 x 512 letterbox, 5 ISP steps with the
 reference's per-step early-exit check, detector, NMS at conf 0.001, matching) on synthetic images and labels — random-init
 weights, so the mAP means nothing; the time per stage does.
-usage: eval_bench.py [images=40] [batch=1] [--match host|device] [--graph] [--confusion]
---match: where detections are matched to labels (run_eval's `match`). --graph: run_eval(graph=True) — the loop as it is meant to
+usage: eval_bench.py [images=40] [batch=1] [--match host|device] [--nms host|device] [--graph] [--confusion]
+--match: where detections are matched to labels (run_eval's `match`). --nms: where NMS runs (run_eval's `nms`; device needs
+--match device). --graph: run_eval(graph=True) — the loop as it is meant to
 be run at batch 1; the stage timers synchronise around every stage and would serialise the pipeline, so they are left out and
 only the time per batch is printed."""
 import argparse, os, sys, time
@@ -20,6 +21,7 @@ ap = argparse.ArgumentParser(description="per-image time of the evaluation loop 
 ap.add_argument("images", nargs="?", type=int, default=40, help="number of batches in the timed run")
 ap.add_argument("batch", nargs="?", type=int, default=1)
 ap.add_argument("--match", choices=("host", "device"), default="host")
+ap.add_argument("--nms", choices=("host", "device"), default="host")
 ap.add_argument("--graph", action="store_true")
 ap.add_argument("--confusion", action="store_true")
 args = ap.parse_args()
@@ -61,7 +63,7 @@ def nms_timed(*a, **k):
 if not GRAPH:
     harness.non_max_suppression = nms_timed
 detector = eng if GRAPH else det_timed
-KW = dict(match=MATCH, graph=GRAPH, confusion=True if CONFUSION else None)
+KW = dict(match=MATCH, nms=args.nms, graph=GRAPH, confusion=True if CONFUSION else None)
 
 data = make_batches(n)                                           # synthetic frames are made before the clock starts
 run_eval(agent, detector, data[:3], cfg, **KW)                   # warm-up
@@ -69,8 +71,8 @@ for k in T: T[k] = 0.0
 torch.cuda.synchronize(); t0 = time.perf_counter()
 res = run_eval(agent, detector, data, cfg, **KW)
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
-print(f"match={MATCH} graph={GRAPH}: {n} batches of {B}: {dt / n * 1e3:.3f} ms per batch ({n * B / dt:.1f} images/s), "
-      f"seen {res['seen']}, map50 {res['map50']:.6f}")
+print(f"match={MATCH} nms={args.nms} graph={GRAPH}: {n} batches of {B}: {dt / n * 1e3:.3f} ms per batch ({n * B / dt:.1f} images/s), "
+      f"seen {res['seen']}, map50 {res['map50']:.6f}, nms_fallbacks {res['nms_fallbacks']}")
 if not GRAPH:
     for k, v in T.items():
         print(f"   {v / n * 1e3:7.2f} ms  {k}")
