@@ -1,7 +1,7 @@
 // Whole Bottleneck in ONE launch:  out = x + SiLU(b2 + W2 (3x3) * SiLU(b1 + W1 (1x1) * x))      C = 256, hidden 128
 // (yolov3/models/common.py:110-120, Bottleneck.forward = x + cv2(cv1(x)); the eight blocks of the C = 256 stage).
 //
-// What the pair [3x3 + residual | next block's 1x1] (yolo_conv_pp.hip, FUSE) leaves on the table, by its own stamps
+// What the pair [3x3 + residual | next block's 1x1] (yolo_tile_pp.h, FUSE) leaves on the table, by its own stamps
 // (profiles/round4_conv_pp_dephase_stamps.txt, 77.9k cycles per 256-px tile): the residual tile arrives cold from HBM in the
 // epilogue (13.5k cycles against 6.4k without one), the hidden tensor h goes to memory and comes back (2 x 30 MB of the
 // launch's 181 MB), and half of the k-loop's LDS-DMA stream re-stages h nine times, once per tap (the k-loop runs at 85 % of
@@ -9,7 +9,7 @@
 // front of its 3x3 — all three go away:
 //   * tile = 16 x 16 output pixels of one image; stage A computes h on the 18 x 18 patch the 3x3 needs (324 px, +27 % of a
 //     layer that is 1/9 of the flops) straight into LDS: h never exists in HBM (launch traffic 181 -> 136 MB);
-//   * stage B is the ping-pong k-loop of yolo_conv_pp.hip with the activation operand read from that patch — the tap is an
+//   * stage B is the ping-pong k-loop of yolo_tile_pp.h with the activation operand read from that patch — the tap is an
 //     address offset — so only the weights stream (2 LDS-DMA instructions per wave and k-tile pair instead of 8);
 //   * the residual is x, which this workgroup read a few microseconds earlier for stage A: an L2 / Infinity-Cache hit.
 //
@@ -28,7 +28,6 @@
 namespace adayolo {
 namespace bnk {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
 #ifdef ADAYOLO_MEASURE
 __device__ unsigned long long g_stamp[4096 * 8];
 #define BN_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_stamp[blockIdx.x * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(512) void k_bneck(const BneckArgs a) {
     read_w(wring, 0, wx);                                // W0 of k-tile 0
     if (wm == 1) barrier();                              // stagger group 1 by one barrier
 
-    // Schedule (yolo_conv_pp.hip without the activation pieces):
+    // Schedule (yolo_tile_pp.h without the activation pieces):
     //   P1(t): reads A(t, px 0)          stages W1(t+1)         P3(t): reads A(t, px 1)       stages W0(t+2)
     //   P2(t): reads W1(t)               waits: W0(t+1) landed  P4(t): reads W0(t+1)          waits: W1(t+1) landed
     auto ktile = [&](unsigned char* cur, unsigned char* oth, int t, bf16x8 (&w0)[4], bf16x8 (&w1)[4]) {
@@ -354,17 +353,9 @@ __global__ __launch_bounds__(512) void k_bneck(const BneckArgs a) {
 template <int ABL>
 static hipError_t launch(BneckArgs a, hipStream_t s) {
     static_assert(kSmem <= 160 * 1024 && kSmem >= 2 * kBufA && kSmem >= kEpi, "LDS budget");
-    auto kern = k_bneck<ABL>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     a.tiles_x = (a.W + TS - 1) / TS;
     a.tiles_y = (a.H + TS - 1) / TS;
-    hipLaunchKernelGGL(kern, dim3(a.B * a.tiles_x * a.tiles_y), dim3(512), kSmem, s, a);
-    return hipGetLastError();
+    return launch_lds<k_bneck<ABL>>(dim3(a.B * a.tiles_x * a.tiles_y), dim3(512), kSmem, s, a);
 }
 
 }  // namespace bnk

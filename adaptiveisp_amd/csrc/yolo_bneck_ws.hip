@@ -347,13 +347,6 @@ template <int CM>
 static hipError_t launch(BwsArgs a, hipStream_t s) {
     using G = Geo<CM>;
     static_assert(G::kSmem <= 160 * 1024, "LDS budget");
-    auto kern = k_bneck_ws<CM>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::kSmem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     a.tiles_x = (a.W + G::TW - 1) / G::TW;
     a.tiles_y = (a.H + G::TH - 1) / G::TH;
     const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
@@ -361,8 +354,7 @@ static hipError_t launch(BwsArgs a, hipStream_t s) {
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (cus <= 0) cus = 256;
     const long grid = ntiles < cus ? ntiles : cus;       // one persistent workgroup per CU
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), G::kSmem, s, a);
-    return hipGetLastError();
+    return launch_lds<k_bneck_ws<CM>>(dim3((unsigned)grid), dim3(512), G::kSmem, s, a);
 }
 
 #ifdef ADAYOLO_MEASURE

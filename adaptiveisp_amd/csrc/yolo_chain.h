@@ -1,5 +1,5 @@
-// Persistent chain of conv layers (yolo_conv_chain.hip: k_conv_chain): what the tile bodies of yolo_conv_pp.hip (256 x 256) and
-// yolo_conv_pp128.hip (256 x 128) share when they run as work items of ONE launch instead of one launch per layer.
+// Persistent chain of conv layers (yolo_conv_chain.hip: k_conv_chain): what the tile bodies of yolo_tile_pp.h (256 x 256) and
+// yolo_tile_pp128.h (256 x 128) share when they run as work items of ONE launch instead of one launch per layer.
 //
 // One work item = one tile of one layer, handed out from a work counter in layer-major order. A tile's outputs leave as
 // written-through (sc1) stores; when the storing waves' vmcnt has reached 0 the tile's ARRIVAL COUNTER (one per layer and

@@ -1,16 +1,8 @@
-// Persistent chain kernel (see yolo_chain.h): tiles of several consecutive conv layers — 256 x 256 tiles of yolo_conv_pp.hip
-// (alone or with the next block's 1x1 fused) and 256 x 128 tiles of yolo_conv_pp128.hip — as work items of ONE launch.
-// The two tile bodies are compiled into this translation unit under their own namespaces (the launch-per-layer kernels of
-// the two files are untouched).
-#include "yolo_device.h"      // ahead of the renaming macros below: nothing in it is renamed
-#define ADAYOLO_TILE_ONLY
-#define pp ppc
-#include "yolo_conv_pp.hip"
-#undef pp
-#define pp128 pp128c
-#include "yolo_conv_pp128.hip"
-#undef pp128
-#undef ADAYOLO_TILE_ONLY
+// Persistent chain kernel (see yolo_chain.h): tiles of several consecutive conv layers — 256 x 256 tiles of yolo_tile_pp.h
+// (alone or with the next block's 1x1 fused) and 256 x 128 tiles of yolo_tile_pp128.h — as work items of ONE launch.
+// The two tile bodies are the ones the launch-per-layer kernels of yolo_conv_pp.hip / yolo_conv_pp128.hip run.
+#include "yolo_tile_pp.h"
+#include "yolo_tile_pp128.h"
 
 namespace adayolo {
 namespace chain {
@@ -18,7 +10,7 @@ namespace chain {
 constexpr int kSmemChain = kChainSmem;
 // the scheduler words sit behind BOTH tile bodies' LDS (ring / epilogue overlay + bias): a change to a tile's pitch, BN or ring
 // must move kChainSchedOff with it
-static_assert(ppc::kSmem <= kChainSchedOff && pp128c::kSmem <= kChainSchedOff, "the chain's scheduler words overlap a tile body's LDS");
+static_assert(pp::kSmem <= kChainSchedOff && pp128::kSmem <= kChainSchedOff, "the chain's scheduler words overlap a tile body's LDS");
 typedef chain_cint_p cint_p;
 #ifdef ADAYOLO_CHAIN_STAMPS
 __device__ unsigned long long g_chain_acc[16];
@@ -31,7 +23,7 @@ __device__ unsigned long long g_chain_acc[16];
 // Dependencies: a tile waits for the m-tiles of the producing layer its input window and its residual rows lie in (arrival
 // counters, bumped when a tile's written-through stores are complete). It only ever waits for items that come before it in
 // the hand-out order, and those are held by workgroups that are running: no deadlock whatever number of workgroups is resident.
-// MSPP / MS128: the MFMA shape of the 256 x 256 / 256 x 128 tile bodies (32 or 16: yolo_conv_pp.hip)
+// MSPP / MS128: the MFMA shape of the 256 x 256 / 256 x 128 tile bodies (32 or 16: yolo_tile_pp.h)
 template <int MSPP, int MS128>
 __global__ __launch_bounds__(512) void k_conv_chain(const ChainArgs c) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -117,9 +109,9 @@ __global__ __launch_bounds__(512) void k_conv_chain(const ChainArgs c) {
 #ifdef ADAYOLO_CHAIN_STAMPS
         PP_STAMP(10);                                        // loop top: item record, slow path, layer arguments
 #endif
-        if (a.chain_tile == 1) pp128c::conv_tile<0, false, true, MS128>(a, hd[1], smem, cx);
-        else if (a.w2) ppc::conv_tile<0, true, true, MSPP>(a, hd[1], smem, cx);
-        else ppc::conv_tile<0, false, true, MSPP>(a, hd[1], smem, cx);
+        if (a.chain_tile == 1) pp128::conv_tile<0, false, true, MS128>(a, hd[1], smem, cx);
+        else if (a.w2) pp::conv_tile<0, true, true, MSPP>(a, hd[1], smem, cx);
+        else pp::conv_tile<0, false, true, MSPP>(a, hd[1], smem, cx);
         cx.pending = hd[2];
         item = __builtin_amdgcn_readfirstlane(sched[0]);
         ready = __builtin_amdgcn_readfirstlane(sched[1]);
@@ -169,16 +161,10 @@ static hipError_t launch_chain(const ChainArgs& c, int grid, hipStream_t s) {
     static_assert(kSmemChain <= 160 * 1024, "LDS budget");
     // each tile type on its family's shape, read when the launch enqueues
     const int mspp = mfma_shape(kShapePp), ms128 = mfma_shape(kShapePp128), which = (mspp == 16 ? 1 : 0) + (ms128 == 16 ? 2 : 0);
-    void (*const kerns[4])(const ChainArgs) = {k_conv_chain<32, 32>, k_conv_chain<16, 32>, k_conv_chain<32, 16>, k_conv_chain<16, 16>};
-    static bool configured[4] = {false, false, false, false};
-    if (!configured[which]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[which]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           kSmemChain);
-        if (e != hipSuccess) return e;
-        configured[which] = true;
-    }
-    hipLaunchKernelGGL(kerns[which], dim3(grid), dim3(512), kSmemChain, s, c);
-    return hipGetLastError();
+    if (which == 0) return launch_lds<k_conv_chain<32, 32>>(dim3(grid), dim3(512), kSmemChain, s, c);
+    if (which == 1) return launch_lds<k_conv_chain<16, 32>>(dim3(grid), dim3(512), kSmemChain, s, c);
+    if (which == 2) return launch_lds<k_conv_chain<32, 16>>(dim3(grid), dim3(512), kSmemChain, s, c);
+    return launch_lds<k_conv_chain<16, 16>>(dim3(grid), dim3(512), kSmemChain, s, c);
 }
 
 }  // namespace chain

@@ -24,8 +24,6 @@
 namespace adayolo {
 namespace dma2 {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
 // ABL: ablation switch for measurements only (0 = real kernel, 1 = no DMA inside the k-loop, 2 = no LDS reads/MFMA)
 // MINW: minimum waves per SIMD the register allocation must allow (2 co-resident workgroups of 8 waves need 4)
 template <int BM, int BN, int WM, int WN, int STAGES, int ABL = 0, int BK = 64, int MINW = 1>
@@ -69,6 +67,8 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_igemm_dma32(const C
         if (m < a.M) {
             // m -> (image, row, column) by multiply-high (ConvArgs::magic_*): two runtime divisions per row cost more
             // than the whole k-loop of a 1x1 layer's tile otherwise
+            // (window_origin / tap_mask / window_offset of yolo_device.h, written out: through them this file's kernels come out
+            // with one more SGPR)
             const int b = a.sh_hw < 0 ? m : (int)(__umulhi((unsigned)m, a.magic_hw) >> a.sh_hw);
             const int rem = m - b * (a.Ho * a.Wo);
             const int ho = a.sh_w < 0 ? rem : (int)(__umulhi((unsigned)rem, a.magic_w) >> a.sh_w);
@@ -270,18 +270,9 @@ static hipError_t launch(ConvArgs a, hipStream_t s) {
     constexpr int ring = STAGES * (BM + BN) * BK * 2, epi = BM * (BN + 8) * 2;
     constexpr int smem = (ring > epi ? ring : epi) + BN * 4;   // the epilogue tile reuses (and may exceed) the ring; + bias
     static_assert(smem <= 160 * 1024, "LDS budget");
-    auto kern = k_conv_igemm_dma32<BM, BN, WM, WN, STAGES, ABL, BK, MINW>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     a.mtiles = (a.M + BM - 1) / BM;
     a.ntiles = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(a.mtiles * a.ntiles), dim3(64 * WM * WN), smem, s, a);
-    return hipGetLastError();
+    return launch_lds<k_conv_igemm_dma32<BM, BN, WM, WN, STAGES, ABL, BK, MINW>>(dim3(a.mtiles * a.ntiles), dim3(64 * WM * WN), smem, s, a);
 }
 
 }  // namespace dma2

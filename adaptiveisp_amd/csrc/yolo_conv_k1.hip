@@ -20,8 +20,6 @@
 namespace adayolo {
 namespace k1 {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
 constexpr int BM = 128, BN = 256;
 constexpr int kOutPitch = BN * 2 + 16;               // bytes per pixel row of the output tile in LDS (2-way write conflicts at most)
 
@@ -122,17 +120,9 @@ template <int K, bool SILU>
 static hipError_t launch(ConvArgs a, hipStream_t s) {
     using G = Geo<K>;
     static_assert(G::kSmem <= 160 * 1024, "LDS budget");
-    auto kern = k_conv_k1<K, SILU>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::kSmem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     a.mtiles = (a.M + BM - 1) / BM;
     a.ntiles = a.Cout / BN;
-    hipLaunchKernelGGL(kern, dim3(a.mtiles * a.ntiles), dim3(512), G::kSmem, s, a);
-    return hipGetLastError();
+    return launch_lds<k_conv_k1<K, SILU>>(dim3(a.mtiles * a.ntiles), dim3(512), G::kSmem, s, a);
 }
 
 }  // namespace k1

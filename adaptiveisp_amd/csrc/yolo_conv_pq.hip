@@ -1,6 +1,6 @@
 // Conv + bias + SiLU (+ residual) — implicit GEMM, 256 px x 128 ch tile, FOUR waves, TWO workgroups per CU.
 //
-// What the ping-pong kernels (yolo_conv_pp.hip / yolo_conv_pp128.hip) cannot hide is everything outside the k-loop: a
+// What the ping-pong kernels (yolo_tile_pp.h / yolo_tile_pp128.h) cannot hide is everything outside the k-loop: a
 // workgroup owns its CU (148 KB LDS, 8 waves x 246 registers), so its prologue (first k-tiles in flight) and its epilogue
 // (SiLU + stores, VALU-issue-bound) leave the matrix pipes idle — 20-28 % of a workgroup's life at K = 1152. The
 // persistent one-wave-per-SIMD form (512 registers, accumulators double-buffered so that a tile drains under the next
@@ -21,12 +21,11 @@
 //   * buffer addressing: 32-bit row offsets against a descriptor; rows beyond M, taps in the zero padding and k-tiles
 //     beyond K use an out-of-range offset (the DMA writes zeros) — no zero page, no 64-bit address arithmetic;
 //   * the bias enters through the matrix pipe (one extra MFMA per accumulator: fp32 bias split into three bf16 terms
-//     against ones), the epilogue is the wave-private LDS transpose of yolo_conv_pp.hip overlaid on the finished ring.
+//     against ones), the epilogue is the wave-private LDS transpose of yolo_ring.h overlaid on the finished ring.
 //
 // Restrictions (the launcher falls back otherwise): Cin % 32 == 0, Cout % 128 == 0, K >= 96, tensors addressable with
 // 32-bit byte offsets, Ho*Wo > 1, Wo > 1.
-#include "yolo_device.h"
-#include <type_traits>
+#include "yolo_ring.h"
 #include <cstdlib>
 
 namespace adayolo {
@@ -90,18 +89,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_pq(const ConvArgs a) {
         const int q = slot ^ ((r >> 2) & 3);
         const int m = m0 + r;
         const int mc = m < a.M ? m : a.M - 1;
-        const int b = (int)(__umulhi((unsigned)mc, a.magic_hw) >> a.sh_hw);
-        const int rem = mc - b * (a.Ho * a.Wo);
-        const int ho = (int)(__umulhi((unsigned)rem, a.magic_w) >> a.sh_w);
-        const int wo = rem - ho * a.Wo;
-        const int hi0 = ho * a.stride - a.pad, wi0 = wo * a.stride - a.pad;
-        unsigned vw = 0, mask = 0;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) vw |= (unsigned)(kw < a.ks && wi0 + kw >= 0 && wi0 + kw < a.W) << kw;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-            mask |= (kh < a.ks && hi0 + kh >= 0 && hi0 + kh < a.H) ? vw << (kh * a.ks) : 0u;
-        mask = m < a.M ? mask : 0u;
+        // (the clamped 32-bit form below counts on the launcher's Ho*Wo > 1 and Wo > 1; window_origin itself also serves divisor 1)
+        int b, hi0, wi0;
+        window_origin(a, mc, b, hi0, wi0);
+        const unsigned mask = m < a.M ? tap_mask(a, hi0, wi0) : 0u;
         vsel[i] = guard + 2u * (unsigned)(((b * a.H + hi0) * a.W + wi0)) * (unsigned)a.in_cs + 16u * (unsigned)q;
         msel[i] = ~mask;
     }
@@ -257,12 +248,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_pq(const ConvArgs a) {
         return;
     }
 
-    // ---- epilogue (see yolo_conv_pp.hip): D[row = channel][col = pixel]; each wave transposes its 128 px x 64 ch through a
-    //      private LDS region (pitch 144 B) and writes 128-byte row segments; activation / residual are compile-time copies
+    // ---- epilogue: each wave transposes its 32 MI px x 64 ch through a private LDS region and writes 128-byte row segments
+    //      (the pieces: yolo_ring.h); activation / residual are compile-time copies; the bias is in the accumulators already
     unsigned char* my = smem + wave * (32 * MI * kEpiPitch);
-    // kKeep (training forward): the tile goes through LDS as the bf16 PRE-activation, is stored to a.pre, then activated from
-    // that rounded value; kDs (backward): the result (+ residual) is dL/d(layer output), stored when a.out is set, and
-    // a.gpre = it * silu'(a.pre) — the contracts of yolo_conv_pp128.hip's epilogue, bit for bit the separate SiLU launches
+    // kKeep (training forward) / kDs (backward): epi_keep / epi_ds, the ONE definition of those contracts (yolo_tile_pp128.h
+    // runs the same)
     auto epilogue = [&](auto silu_tag, auto res_tag, auto keep_tag, auto ds_tag) __attribute__((always_inline)) {
         constexpr bool kKeep = decltype(keep_tag)::value, kAct = decltype(silu_tag)::value, kDs = decltype(ds_tag)::value;
         constexpr bool kSilu = kAct && !kKeep, kRes = decltype(res_tag)::value;
@@ -271,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_pq(const ConvArgs a) {
         unsigned short* const op = a.out + (long)mrow * a.out_cs + n;
         const unsigned short* const rp = kRes ? a.res + (long)mrow * a.res_cs + n : nullptr;
         const long ostep = 8L * a.out_cs, rstep = kRes ? 8L * a.res_cs : 0;
-        unsigned char* const wr = my + (lane & 31) * kEpiPitch + 8 * (lane >> 5);
+        unsigned char* const wr = epi_wr<32>(my, lane);
         const unsigned char* const rd = my + r0 * kEpiPitch + chunk * 16;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
@@ -286,57 +276,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_pq(const ConvArgs a) {
                     if (ok[it]) r[it] = *reinterpret_cast<const u32x4*>(rp + (4 * mi + it) * rstep);
                 }
             }
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    f32x2 x0 = {acc[ni][mi][4 * qd], acc[ni][mi][4 * qd + 1]}, x1 = {acc[ni][mi][4 * qd + 2], acc[ni][mi][4 * qd + 3]};
-                    if (kSilu) { x0 = silu_pk(x0); x1 = silu_pk(x1); }
-                    *reinterpret_cast<u32x2*>(wr + mi * 32 * kEpiPitch + (ni * 32 + 8 * qd) * 2) =
-                        u32x2{pack_bf16x2(x0.x, x0.y), pack_bf16x2(x1.x, x1.y)};
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int it = 0; it < 4; ++it) v[it] = *reinterpret_cast<const u32x4*>(rd + (mi * 32 + it * 8) * kEpiPitch);
-            if (kKeep) {
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    if (ok[it]) *reinterpret_cast<u32x4*>(a.pre + (long)(mrow + 8 * (4 * mi + it)) * a.pre_cs + n) = v[it];
-                    if (kAct) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[it][j] = silu_bf16x2(v[it][j]);
-                    }
-                }
-            }
-            if (kRes) {
-#pragma unroll
-                for (int it = 0; it < 4; ++it)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const f32x2 x = f32x2{__uint_as_float(v[it][j] << 16), __uint_as_float(v[it][j] & 0xFFFF0000u)} +
-                                        f32x2{__uint_as_float(r[it][j] << 16), __uint_as_float(r[it][j] & 0xFFFF0000u)};
-                        v[it][j] = pack_bf16x2(x.x, x.y);
-                    }
-            }
+            epi_put<kSilu>(acc, mi, wr);
+            epi_rows(rd, mi, v);
+            if (kKeep) epi_keep<kAct>(a, mrow, n, mi, ok, v);
+            if (kRes) epi_add_res(v, r);
             if (kDs) {
-                u32x4 p[4];
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    p[it] = u32x4{0u, 0u, 0u, 0u};
-                    if (ok[it]) p[it] = *reinterpret_cast<const u32x4*>(a.pre + (long)(mrow + 8 * (4 * mi + it)) * a.pre_cs + n);
-                }
-                if (a.out) {
-#pragma unroll
-                    for (int it = 0; it < 4; ++it)
-                        if (ok[it]) __builtin_nontemporal_store(v[it], reinterpret_cast<u32x4*>(op + (4 * mi + it) * ostep));
-                }
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[it][j] = dsilu_bf16x2(v[it][j], p[it][j]);
-                    if (ok[it])
-                        __builtin_nontemporal_store(v[it], reinterpret_cast<u32x4*>(a.gpre + (long)(mrow + 8 * (4 * mi + it)) * a.gpre_cs + n));
-                }
+                epi_ds(a, mrow, n, mi, ok, op, ostep, v);   // (no depth-to-space form here: the launcher refuses d2s_c)
                 continue;
             }
 #pragma unroll
@@ -363,22 +308,12 @@ static hipError_t launch(ConvArgs a, hipStream_t s) {
     constexpr int kSmem = Geo<MI>::kSmem;
     static_assert(2 * kSmem <= 160 * 1024, "two workgroups per CU");
     a.mtiles = (a.M + Geo<MI>::BM - 1) / Geo<MI>::BM;
-    auto kern = k_conv_pq<ABL, MI>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kSmem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     int smem_bytes = kSmem;
 #ifdef ADAYOLO_MEASURE
     static const int extra = getenv("ADAYOLO_PQ_EXTRA_SMEM") ? atoi(getenv("ADAYOLO_PQ_EXTRA_SMEM")) : 0;   // > 8 KB: one workgroup per CU
     smem_bytes += extra;
-    if (extra) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
 #endif
-    hipLaunchKernelGGL(kern, dim3(a.mtiles * a.ntiles), dim3(256), smem_bytes, s, a);
-    return hipGetLastError();
+    return launch_lds<k_conv_pq<ABL, MI>>(dim3(a.mtiles * a.ntiles), dim3(256), smem_bytes, s, a);
 }
 
 }  // namespace pq

@@ -11,8 +11,6 @@
 namespace adayolo {
 namespace smallk {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
 // swizzle key of a tile row whose rows are CIN*2 bytes (64 B -> 4 rows per 256-B bank row, 128 B -> 2)
 template <int CIN>
 __device__ __forceinline__ int row_key(int r) {
@@ -178,18 +176,9 @@ static hipError_t launch(ConvArgs a, hipStream_t s) {
     constexpr int ring = pbytes + 9 * BN * CIN * 2, epi = TPH * TPW * (BN + 8) * 2;
     constexpr int smem = (ring > epi ? ring : epi) + BN * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    auto kern = k_conv3x3_small<CIN, BN, S, TPH, TPW, WM, WN>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     const int tiles_x = (a.Wo + TPW - 1) / TPW, tiles_y = (a.Ho + TPH - 1) / TPH;
     const int ntn = (a.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(a.B * tiles_y * tiles_x * ntn), dim3(64 * WM * WN), smem, s, a, tiles_x, tiles_y);
-    return hipGetLastError();
+    return launch_lds<k_conv3x3_small<CIN, BN, S, TPH, TPW, WM, WN>>(dim3(a.B * tiles_y * tiles_x * ntn), dim3(64 * WM * WN), smem, s, a, tiles_x, tiles_y);
 }
 
 }  // namespace smallk

@@ -268,13 +268,6 @@ static hipError_t launch(ConvArgs a, hipStream_t s) {
     constexpr int RPD = 64 / (CIN / 8), PINS = (PROWS + RPD - 1) / RPD, PBYTES = PINS * RPD * CIN * 2;
     constexpr int smem = 2 * PBYTES + kOutBytes + BN * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    auto kern = k_conv_ws<CIN, RES>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
     const int nchunks = a.Cout / BN;
     const long ntiles = (long)a.B * tiles_y * tiles_x;
@@ -283,8 +276,7 @@ static hipError_t launch(ConvArgs a, hipStream_t s) {
     long per_chunk = 256 / nchunks;
     if (per_chunk < 1) per_chunk = 1;
     if (per_chunk > ntiles) per_chunk = ntiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(per_chunk * nchunks)), dim3(512), smem, s, a, tiles_x, tiles_y, nchunks);
-    return hipGetLastError();
+    return launch_lds<k_conv_ws<CIN, RES>>(dim3((unsigned)(per_chunk * nchunks)), dim3(512), smem, s, a, tiles_x, tiles_y, nchunks);
 }
 
 #ifdef ADAYOLO_MEASURE

@@ -38,6 +38,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
+// the zero page: 16 bytes an LDS-DMA piece reads where its tile row has nothing to fetch (rows beyond M, taps in the padding,
+// k-tiles beyond K). Internal linkage: one copy per translation unit that uses it, none elsewhere
+[[maybe_unused]] static __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
 // branch-free choice between a tensor address and the zero page
 __device__ __forceinline__ unsigned long long sel(bool ok, unsigned long long p, unsigned long long z) {
     const unsigned long long m = ok ? ~0ull : 0ull;
@@ -80,15 +83,43 @@ constexpr unsigned kDescFlags = 0x00020000u;
 // bytes per pixel row of a wave's epilogue region in LDS: 64 channels of bf16 + 16 bytes of pad (conflict-free ds_read_b128)
 constexpr int kEpiPitch = 144;
 
+// ---- implicit-GEMM row addressing ---------------------------------------------------------------------------------------
+// output pixel m -> (image, row, column) by multiply-high (ConvArgs::magic_*): the two runtime divisions cost ~80 VALU each
+__device__ __forceinline__ void pixel_split(const ConvArgs& a, int m, int& b, int& ho, int& wo) {
+    b = a.sh_hw < 0 ? m : (int)(__umulhi((unsigned)m, a.magic_hw) >> a.sh_hw);
+    const int rem = m - b * (a.Ho * a.Wo);
+    ho = a.sh_w < 0 ? rem : (int)(__umulhi((unsigned)rem, a.magic_w) >> a.sh_w);
+    wo = rem - ho * a.Wo;
+}
+// ... and the input pixel (hi0, wi0) its window starts at (negative in the padding)
+__device__ __forceinline__ void window_origin(const ConvArgs& a, int m, int& b, int& hi0, int& wi0) {
+    int ho, wo;
+    pixel_split(a, m, b, ho, wo);
+    hi0 = ho * a.stride - a.pad; wi0 = wo * a.stride - a.pad;
+}
+// bit tap = kh * ks + kw: that tap of the window lies inside the image. Validity is separable: rows x columns
+__device__ __forceinline__ unsigned tap_mask(const ConvArgs& a, int hi0, int wi0) {
+    unsigned vw = 0, mask = 0;
+    // ks <= 3 (1 or 3 at the ABI; 2 for the stride-2 data gradient): three straight-line taps, no loop
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) vw |= (unsigned)(kw < a.ks && wi0 + kw >= 0 && wi0 + kw < a.W) << kw;
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+        mask |= (kh < a.ks && hi0 + kh >= 0 && hi0 + kh < a.H) ? vw << (kh * a.ks) : 0u;
+    return mask;
+}
+// element offset of the window's first pixel in the input tensor (64-bit; only dereferenced where the mask allows)
+__device__ __forceinline__ long window_offset(const ConvArgs& a, int b, int hi0, int wi0) {
+    return ((long)b * a.H * a.W + (long)hi0 * a.W + wi0) * a.in_cs;
+}
+
 // ---- epilogue math ------------------------------------------------------------------------------------------------------
 // (pixel, channel) of an epilogue element in the tensors it addresses: the identity, or ConvArgs' depth-to-space map
 __device__ __forceinline__ void epilogue_pos(const ConvArgs& a, int m, int n, long& pix, int& nn) {
     pix = m; nn = n;
     if (a.d2s_c) {
-        const int b = a.sh_hw < 0 ? m : (int)(__umulhi((unsigned)m, a.magic_hw) >> a.sh_hw);
-        const int rem = m - b * (a.Ho * a.Wo);
-        const int i = a.sh_w < 0 ? rem : (int)(__umulhi((unsigned)rem, a.magic_w) >> a.sh_w);
-        const int j = rem - i * a.Wo;
+        int b, i, j;
+        pixel_split(a, m, b, i, j);
         const int p = n / a.d2s_c;
         nn = n - p * a.d2s_c;
         pix = ((long)(b * 2 * a.Ho + 2 * i + (p >> 1))) * (2 * a.Wo) + 2 * j + (p & 1);
@@ -124,14 +155,17 @@ __device__ __forceinline__ unsigned dsilu_bf16x2(unsigned g, unsigned p) {
                      dsilu_f32(__uint_as_float(g & 0xFFFF0000u), __uint_as_float(p & 0xFFFF0000u))};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(y, bf16x2));
 }
-// four consecutive channels: + bias, SiLU (compile-time), round to bf16 (v_cvt_pk_bf16_f32) -> two packed words
+// four consecutive channels: SiLU (compile-time), round to bf16 (v_cvt_pk_bf16_f32) -> two packed words
 template <bool SILU>
-__device__ __forceinline__ void bias_act_pack4(float a0, float a1, float a2, float a3, const float4 b, unsigned& lo, unsigned& hi) {
-    f32x2 x0 = f32x2{a0, a1} + f32x2{b.x, b.y};
-    f32x2 x1 = f32x2{a2, a3} + f32x2{b.z, b.w};
+__device__ __forceinline__ void act_pack4(f32x2 x0, f32x2 x1, unsigned& lo, unsigned& hi) {
     if (SILU) { x0 = silu_pk(x0); x1 = silu_pk(x1); }
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(x0, bf16x2));
     hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x1, bf16x2));
+}
+// ... behind the bias add
+template <bool SILU>
+__device__ __forceinline__ void bias_act_pack4(float a0, float a1, float a2, float a3, const float4 b, unsigned& lo, unsigned& hi) {
+    act_pack4<SILU>(f32x2{a0, a1} + f32x2{b.x, b.y}, f32x2{a2, a3} + f32x2{b.z, b.w}, lo, hi);
 }
 
 }  // namespace adayolo

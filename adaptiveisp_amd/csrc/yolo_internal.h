@@ -21,14 +21,14 @@ struct ConvArgs {
     // division by Ho*Wo and by Wo as multiply-high + shift (exact for 0 <= n < 2^31; sh < 0: divisor is 1)
     unsigned magic_hw, magic_w;
     int sh_hw, sh_w;
-    // fused second layer (yolo_conv_pp.hip, Cout == 256 only): a 1x1 conv 256 -> 128 + bias + SiLU applied to this conv's
+    // fused second layer (yolo_tile_pp.h, Cout == 256 only): a 1x1 conv 256 -> 128 + bias + SiLU applied to this conv's
     // OUTPUT tile while it is in LDS (Bottleneck.cv1 of the next block); null = not fused
     const unsigned short* w2; const float* bias2;
     unsigned short* out2; int out2_cs;
-    // training forward (yolo_conv_dma2.hip / yolo_conv_pp128.hip): when set, the bf16 pre-activation (conv + bias) is stored
+    // training forward (yolo_conv_dma2.hip / epi_keep of yolo_ring.h): when set, the bf16 pre-activation (conv + bias) is stored
     // here and the activation is applied to that ROUNDED value — bit for bit what adayolo_silu_fwd makes of it
     unsigned short* pre; int pre_cs;
-    // split-K (yolo_conv_pp128.hip, variants 100 + S): S workgroups per output tile, fp32 partial tiles + one ticket per tile
+    // split-K (yolo_tile_pp128.h, variants 100 + S): S workgroups per output tile, fp32 partial tiles + one ticket per tile
     // in the caller's workspace; 1 = every other kernel
     float* partial = nullptr; int* tickets = nullptr; int ksplit = 1;
     // backward of the frozen detector (variants of the keep set): when gpre is set, `pre` is an INPUT (the layer's saved
@@ -39,10 +39,25 @@ struct ConvArgs {
     // are the four pixel parities of the (large) input-gradient tensor: d2s_c = C > 0 makes the epilogue address out / res /
     // pre / gpre depth-to-space — channel group p of pixel (b, i, j) is pixel (b, 2i + p/2, 2j + p%2) of [B, 2Ho, 2Wo, C]
     int d2s_c = 0;
-    // persistent chain (yolo_conv_chain.hip): which tile body runs this layer's items — 0: 256 x 256 (yolo_conv_pp.hip),
-    // 1: 256 x 128 (yolo_conv_pp128.hip)
+    // persistent chain (yolo_conv_chain.hip): which tile body runs this layer's items — 0: 256 x 256 (yolo_tile_pp.h),
+    // 1: 256 x 128 (yolo_tile_pp128.h)
     int chain_tile = 0;
 };
+
+// One launch of a kernel whose dynamic LDS exceeds the 64 KB default. The attribute that allows it is set once per kernel — one
+// instantiation of this template, hence one counter, per Kern (idempotent, benign if raced) — and again only if a launch asks
+// for more than any before it (the measurement builds' *_EXTRA_SMEM switches).
+template <auto Kern, class... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, int smem, hipStream_t s, const Args&... args) {
+    static int allowed = 0;
+    if (smem > allowed) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) return e;
+        allowed = smem;
+    }
+    hipLaunchKernelGGL(Kern, grid, block, smem, s, args...);
+    return hipGetLastError();
+}
 
 // ---- persistent chain (yolo_conv_chain.hip: k_conv_chain): consecutive layers' tiles (256 x 256, 256 x 128) in ONE launch.
 // One work item = one tile of one layer; the tables are built on the host (yolo_api.hip: adayolo_conv_chain_prepare).

@@ -288,25 +288,16 @@ __global__ __launch_bounds__(256, 4) void k_stem_down(const float* __restrict__ 
 hipError_t launch_stem_down(const float* img, const float* w0, const float* b0, const void* w1, const float* b1, void* out,
                             int out_cs, int B, int H, int W, int Hp, int pad_top, float pad_value, const void* w2,
                             const float* b2, void* out2, int out2_cs, hipStream_t s) {
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sd::k_stem_down),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, sd::kSmem);
-        if (e != hipSuccess) return e;
-        configured = true;
-    }
     const int Ho = Hp / 2, Wo = W / 2;
     dim3 grid((Wo + sd::TX - 1) / sd::TX, (Ho + sd::TY - 1) / sd::TY, B);
     int smem_bytes = sd::kSmem;
 #ifdef ADAYOLO_MEASURE
     static const int extra = getenv("ADAYOLO_SD_EXTRA_SMEM") ? atoi(getenv("ADAYOLO_SD_EXTRA_SMEM")) : 0;   // > 1 KB: three workgroups per CU
     smem_bytes += extra;
-    if (extra) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sd::k_stem_down), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
 #endif
-    hipLaunchKernelGGL(sd::k_stem_down, grid, dim3(256), smem_bytes, s, img, w0, b0, static_cast<const unsigned short*>(w1), b1,
-                       static_cast<unsigned short*>(out), out_cs, H, W, Hp, pad_top, pad_value,
-                       static_cast<const unsigned short*>(w2), b2, static_cast<unsigned short*>(out2), out2_cs);
-    return hipGetLastError();
+    return launch_lds<sd::k_stem_down>(grid, dim3(256), smem_bytes, s, img, w0, b0, static_cast<const unsigned short*>(w1), b1,
+                                       static_cast<unsigned short*>(out), out_cs, H, W, Hp, pad_top, pad_value,
+                                       static_cast<const unsigned short*>(w2), b2, static_cast<unsigned short*>(out2), out2_cs);
 }
 
 #ifdef ADAYOLO_MEASURE

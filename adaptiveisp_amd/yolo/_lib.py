@@ -66,14 +66,17 @@ class NmsBatchArgs(ctypes.Structure):              # adayolo_nms_batch_args
 NMS_MULTI_LABEL, NMS_AGNOSTIC, NMS_OVERFLOW = 1, 2, 1
 
 
-def load():
+def load(path=None):
+    """The library with its entry points declared. path: another build of it (the A/B tools), declared the same way and handed
+    back without becoming the process's library."""
     global _lib
-    if _lib is not None:
+    if path is None and _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise AdayoloError(f"{LIB_PATH} not found: run __graft_entry__.build() (hipcc --offload-arch=gfx950); "
+    lib_path = path or LIB_PATH
+    if not os.path.exists(lib_path):
+        raise AdayoloError(f"{lib_path} not found: run __graft_entry__.build() (hipcc --offload-arch=gfx950); "
                            "the detector has no eager fallback")
-    L = ctypes.CDLL(LIB_PATH)
+    L = ctypes.CDLL(lib_path)
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     L.adayolo_conv_fwd.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
     L.adayolo_conv_fwd_variant.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
@@ -152,7 +155,8 @@ def load():
         getattr(L, n).restype = ci
     if L.adayolo_abi_version() != ABI_VERSION:
         raise AdayoloError("libadayolo.so ABI mismatch: rebuild")
-    _lib = L
+    if path is None:
+        _lib = L
     return L
 
 

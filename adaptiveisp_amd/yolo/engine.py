@@ -515,7 +515,7 @@ class YoloEngine:
         """Runs of consecutive launches of the 256 x 256 kernel (variant 50, alone or with the next block's 1x1 fused) and the
         256 x 128 kernel (variant 60) — the backbone from its C = 256 stage through the C = 512 stage, the head's blocks — as ONE
         persistent launch each (adayolo_conv_chain_fwd,
-        csrc/yolo_conv_pp.hip: k_conv_chain): tiles of all the run's layers drawn from one work counter, a tile waiting only for
+        csrc/yolo_conv_chain.hip: k_conv_chain): tiles of all the run's layers drawn from one work counter, a tile waiting only for
         the producer tiles its input window / residual rows lie in. Bit-identical to the separate launches (same tile code).
         ADAYOLO_CHAIN=0 keeps the launches separate. Returns the number of chains."""
         # chains of an earlier plan that are still IN the plan stay registered; the others are dropped (a re-plan must not leave

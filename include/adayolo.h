@@ -66,7 +66,7 @@ int adayolo_conv_fwd(const void* in, int in_cstride,
                      int ksize, int stride, int act, void* stream);
 
 /*
- * A CHAIN of consecutive conv layers in ONE persistent launch (csrc/yolo_conv_pp.hip: k_conv_chain). Each layer is what
+ * A CHAIN of consecutive conv layers in ONE persistent launch (csrc/yolo_conv_chain.hip: k_conv_chain). Each layer is what
  * adayolo_conv_fwd (weight2 == NULL) or adayolo_conv_fused1x1_fwd computes — Conv/Bottleneck of yolov3/models/common.py:45-59,
  * 110-120 — on the 256 px x 256 ch kernel (tile 0: Cin % 64 == 0, Cout % 256 == 0; fused: Cout == 256, Cout2 == 128, weight2
  * fragment-major as below) or the 256 px x 128 ch kernel (tile 1: Cin % 64 == 0, Cout % 128 == 0, not fused). One workgroup per

@@ -1,4 +1,4 @@
-"""Persistent chain of 256 x 256-tile conv layers (adayolo_conv_chain_*, csrc/yolo_conv_pp.hip: k_conv_chain) against the SAME
+"""Persistent chain of 256 x 256-tile conv layers (adayolo_conv_chain_*, csrc/yolo_conv_chain.hip: k_conv_chain) against the SAME
 layers launched one by one (adayolo_conv_fwd_variant 50 / adayolo_conv_fused1x1_fwd — themselves pinned against fp32 F.conv2d
 in test_gpu_yolo_variants.py, i.e. Conv / Bottleneck of yolov3/models/common.py:45-59,110-120): the tile code is the same, so
 the results must be BIT-identical; what is tested is the chain's own machinery — work counter, arrival counters over halo and
@@ -34,6 +34,8 @@ def _check(net, run, want, tag):
 
 class _Net:
     """x -(3x3 s1 c0->256, +1x1)-> x0,h0 -(3x3 128->256 + x0, +1x1)-> x1,h1 ... -(3x3 128->256 + x_{n-1})-> x_n -(3x3 s2 256->512)-> y"""
+
+    act = 1                         # every layer's activation (ACT_SILU; a test may set ACT_NONE on a net before it runs it)
 
     def __init__(self, B, H, W, c0=64, blocks=3, tail=True, seed=0):
         self.B, self.H, self.W = B, H, W
@@ -73,7 +75,7 @@ class _Net:
             Bq, Hq, Wq, _ = ly["inp"].shape
             common = (vp(ly["inp"].data_ptr()), ly["cin"], vp(ly["w"].data_ptr()), vp(ly["b"].data_ptr()),
                       vp(ly["res"].data_ptr()) if ly["res"] is not None else None, ly["cout"] if ly["res"] is not None else 0,
-                      vp(ly["out"].data_ptr()), ly["cout"], Bq, Hq, Wq, ly["cin"], ly["cout"], ly["k"], ly["s"], _lib.ACT_SILU)
+                      vp(ly["out"].data_ptr()), ly["cout"], Bq, Hq, Wq, ly["cin"], ly["cout"], ly["k"], ly["s"], self.act)
             if "w2" in ly:
                 rc = L.adayolo_conv_fused1x1_fwd(*common, vp(ly["w2p"].data_ptr()), vp(ly["b2"].data_ptr()), vp(ly["out2"].data_ptr()), 128, 128, st)
             else:
@@ -90,7 +92,7 @@ class _Net:
             c.in_, c.in_cstride, c.weight, c.bias = ly["inp"].data_ptr(), ly["cin"], ly["w"].data_ptr(), ly["b"].data_ptr()
             c.residual, c.res_cstride = (ly["res"].data_ptr(), ly["cout"]) if ly["res"] is not None else (None, 0)
             c.out, c.out_cstride = ly["out"].data_ptr(), ly["cout"]
-            c.B, c.H, c.W, c.Cin, c.Cout, c.ksize, c.stride, c.act = Bq, Hq, Wq, ly["cin"], ly["cout"], ly["k"], ly["s"], _lib.ACT_SILU
+            c.B, c.H, c.W, c.Cin, c.Cout, c.ksize, c.stride, c.act = Bq, Hq, Wq, ly["cin"], ly["cout"], ly["k"], ly["s"], self.act
             c.tile = ly.get("tile", 0)
             if "w2" in ly:
                 c.weight2, c.bias2, c.out2, c.out2_cstride, c.Cout2 = ly["w2p"].data_ptr(), ly["b2"].data_ptr(), ly["out2"].data_ptr(), 128, 128

@@ -151,24 +151,25 @@ def test_fused_pair_first_layer_is_the_unfused_kernel(case, ms):
     w2p = w2.reshape(4, 32, 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
     Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    with mfma_shape(pp=ms):
-        first = None
-        for _ in range(4):
-            out = torch.full((B, Ho, Wo, 256), float("nan"), dtype=torch.bfloat16, device=DEV)
-            out2 = torch.full((B, Ho, Wo, 128), float("nan"), dtype=torch.bfloat16, device=DEV)
-            rc = L.adayolo_conv_fused1x1_fwd(P(x), cin, P(w), P(b), P(res), 256 if use_res else 0, P(out), 256, B, H, W, cin, 256,
-                                             k, s, 1, P(w2p), P(b2), P(out2), 128, 128, _lib.stream_ptr())
-            _lib.check(rc, "fused conv")
-            torch.cuda.synchronize()
-            if first is None:
-                first = (out, out2)
-            else:
-                assert torch.equal(first[0].view(torch.int16), out.view(torch.int16)), "run-to-run difference (out)"
-                assert torch.equal(first[1].view(torch.int16), out2.view(torch.int16)), "run-to-run difference (out2)"
-        out, out2 = first
-        sep = _run_variant(x, w, b, res, k, s, 1, 50, reps=1)
-    assert torch.equal(sep.view(torch.int16), out.view(torch.int16)), "first layer differs from the unfused kernel"
-    _vs_fp32(f"fused {case} shape {ms} out2", out2, _reference(out, w2, b2, None, 1, 1, 1))
+    for act in (1, 0):                                   # the first layer's activation: SiLU (the engine's use), none
+        with mfma_shape(pp=ms):
+            first = None
+            for _ in range(4):
+                out = torch.full((B, Ho, Wo, 256), float("nan"), dtype=torch.bfloat16, device=DEV)
+                out2 = torch.full((B, Ho, Wo, 128), float("nan"), dtype=torch.bfloat16, device=DEV)
+                rc = L.adayolo_conv_fused1x1_fwd(P(x), cin, P(w), P(b), P(res), 256 if use_res else 0, P(out), 256, B, H, W, cin, 256,
+                                                 k, s, act, P(w2p), P(b2), P(out2), 128, 128, _lib.stream_ptr())
+                _lib.check(rc, "fused conv")
+                torch.cuda.synchronize()
+                if first is None:
+                    first = (out, out2)
+                else:
+                    assert torch.equal(first[0].view(torch.int16), out.view(torch.int16)), "run-to-run difference (out)"
+                    assert torch.equal(first[1].view(torch.int16), out2.view(torch.int16)), "run-to-run difference (out2)"
+            out, out2 = first
+            sep = _run_variant(x, w, b, res, k, s, act, 50, reps=1)
+        assert torch.equal(sep.view(torch.int16), out.view(torch.int16)), "first layer differs from the unfused kernel"
+        _vs_fp32(f"fused {case} shape {ms} act{act} out2", out2, _reference(out, w2, b2, None, 1, 1, 1))
 
 
 @pytest.mark.parametrize("ms", [32, 16])
@@ -220,7 +221,10 @@ def test_chain_equals_its_separate_launches(pp, pp128):
     """The smallest nets of test_gpu_yolo_chain.py (256 x 256 tiles with fused pairs; the mixed 256 x 256 / 256 x 128 net): the
     chain uses each tile type's selected shape, so it is bit-identical to the launch-per-layer run under the same setting."""
     with mfma_shape(pp, pp128):
-        for net in (_Net(1, 16, 16, 64, 2, seed=116), _Net512(1, 20, 24, 256, 1, seed=30)):
+        # ... with SiLU layers (the engine's chains), and with act none: the chain's other four epilogue forms per tile type
+        for net, act in ((_Net(1, 16, 16, 64, 2, seed=116), 1), (_Net512(1, 20, 24, 256, 1, seed=30), 1),
+                         (_Net(1, 16, 16, 64, 2, seed=117), 0), (_Net512(1, 20, 24, 256, 1, seed=31), 0)):
+            net.act = act
             net.poison()
             net.run_separately()
             torch.cuda.synchronize()

@@ -1,5 +1,6 @@
 """Detector training path on HIP: element-wise training kernels against PyTorch, and the whole backward (raw head
 maps -> gradient of the input image) against fp32 autograd of the plain module tree."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -249,17 +250,45 @@ def test_fused_detection_loss_matches_the_pytorch_loss(B, H, W, dup):
         stale.sum().backward()
 
 
-@pytest.mark.parametrize("variant", [5, 22, 26, 27, 60, 80, 85])
-def test_conv_keep_fwd_equals_conv_then_silu(variant):
+def _variants_and_shapes(variants):
+    """Every variant at the process's MFMA shape (the ids the cases always had), and the 256 px x 128 ch ring kernel (60, split-K
+    104), whose backward epilogues exist once per shape, under each shape explicitly."""
+    return [pytest.param(v, None, id=str(v)) for v in variants] + [pytest.param(v, ms, id=f"{v}-ms{ms}") for v in (60, 104) for ms in (32, 16)]
+
+
+@contextlib.contextmanager
+def _mfma_shape_pp128(ms):
+    """adayolo_set_mfma_shape(1, ms) for the block (None: leave it), the earlier setting restored behind it."""
+    from adaptiveisp_amd.yolo import _lib
+    L = _lib.load()
+    old = L.adayolo_get_mfma_shape(1)
+    try:
+        if ms is not None:
+            assert L.adayolo_set_mfma_shape(1, ms) == 0 and L.adayolo_get_mfma_shape(1) == ms
+        yield
+    finally:
+        L.adayolo_set_mfma_shape(1, old)
+
+
+@pytest.mark.parametrize("variant,ms", [pytest.param(v, None, id=str(v)) for v in (5, 22, 26, 27, 60, 80, 85)] +
+                         [pytest.param(60, 32, id="60-ms32"), pytest.param(60, 16, id="60-ms16")])
+def test_conv_keep_fwd_equals_conv_then_silu(variant, ms):
     """adayolo_conv_keep_fwd (one launch: pre-activation stored, activation applied to its bf16 value, residual added) ==
-    adayolo_conv_fwd_variant(ACT_NONE) into `pre` + adayolo_silu_fwd, bit for bit, on every shape the kernel serves."""
+    adayolo_conv_fwd_variant(ACT_NONE) into `pre` + adayolo_silu_fwd, bit for bit, on every shape the kernel serves; ms: the MFMA
+    shape of the 256 px x 128 ch kernel (None: the process's)."""
+    with _mfma_shape_pp128(ms):
+        _conv_keep_case(variant)
+
+
+def _conv_keep_case(variant):
     from adaptiveisp_amd.yolo import _lib
     L = _lib.load()
     st = _lib.stream_ptr()
     served = 0
     for (B, H, W, cin, cout, k, s, use_res, act) in [(2, 16, 16, 512, 1024, 3, 1, True, 1), (8, 64, 64, 128, 256, 3, 1, False, 1),
                                                     (3, 33, 17, 256, 128, 1, 1, True, 1), (2, 32, 32, 256, 512, 3, 2, False, 1),
-                                                    (1, 9, 7, 128, 128, 3, 1, True, 0), (2, 40, 24, 64, 128, 1, 1, False, 1)]:
+                                                    (1, 9, 7, 128, 128, 3, 1, True, 0), (2, 40, 24, 64, 128, 1, 1, False, 1),
+                                                    (1, 9, 7, 128, 128, 3, 1, False, 0)]:      # act none without a residual
         g = torch.Generator().manual_seed(H * 7 + cin)
         x = torch.randn(B, H, W, cin, generator=g).to(torch.bfloat16).to(DEV)
         w = (torch.randn(cout, k, k, cin, generator=g) / (k * k * cin) ** 0.5).to(torch.bfloat16).to(DEV)
@@ -342,17 +371,25 @@ def test_graph_replay_and_fused_train_forward_change_nothing():
     assert torch.equal(grad_a, grad_b)
 
 
-@pytest.mark.parametrize("variant", [5, 22, 26, 27, 60, 80, 85, 104])
-def test_conv_dsilu_fwd_equals_conv_then_silu_bwd(variant):
+@pytest.mark.parametrize("variant,ms", _variants_and_shapes([5, 22, 26, 27, 60, 80, 85, 104]))
+def test_conv_dsilu_fwd_equals_conv_then_silu_bwd(variant, ms):
     """adayolo_conv_dsilu_fwd (one launch: g = conv + residual rounded to bf16, optionally stored; grad_pre = g * silu'(pre))
     == adayolo_conv_fwd_variant(ACT_NONE) + adayolo_silu_bwd, bit for bit, with and without the stored gradient, on
-    channel slices, on every shape the kernel serves (the split-K variant with its workspace)."""
+    channel slices, on every shape the kernel serves (the split-K variant with its workspace); ms: the MFMA shape of the
+    256 px x 128 ch kernel's k-loop and epilogue (None: the process's)."""
+    with _mfma_shape_pp128(ms):
+        _conv_dsilu_case(variant)
+
+
+def _conv_dsilu_case(variant):
     from adaptiveisp_amd.yolo import _lib
     L = _lib.load()
     st = _lib.stream_ptr()
     served = 0
+    # (2, 13, 17, 256, 128, k3): M = 442, nK = 36 — the small shape split-K (S = 4) serves
     for (B, H, W, cin, cout, k, use_res) in [(8, 16, 16, 1024, 512, 3, True), (8, 32, 32, 512, 256, 3, False), (3, 33, 17, 256, 128, 1, True),
-                                             (1, 9, 7, 128, 128, 3, False), (2, 40, 24, 128, 64, 1, True), (2, 24, 40, 64, 32, 3, False)]:
+                                             (1, 9, 7, 128, 128, 3, False), (2, 40, 24, 128, 64, 1, True), (2, 24, 40, 64, 32, 3, False),
+                                             (2, 13, 17, 256, 128, 3, True)]:
         ws, nws = None, 0
         if variant >= 100:
             nws = int(L.adayolo_conv_splitk_workspace_bytes(B, H, W, cin, cout, k, 1, variant))
@@ -399,10 +436,15 @@ def test_conv_dsilu_fwd_equals_conv_then_silu_bwd(variant):
                                     k, 1, 5, None, 0, st) == -1
 
 
-@pytest.mark.parametrize("variant", [5, 27, 60, 104])
-def test_stride2_data_gradient_without_zero_insertion(variant):
+@pytest.mark.parametrize("variant,ms", _variants_and_shapes([5, 27, 60, 104]))
+def test_stride2_data_gradient_without_zero_insertion(variant, ms):
     """adayolo_conv_s2grad_fwd (2x2 conv over the output grid, depth-to-space stores) against fp32 autograd of the stride-2
-    conv, with a residual, with the fused SiLU' (grad_in stored and not), on channel slices; ragged pixel counts."""
+    conv, with a residual, with the fused SiLU' (grad_in stored and not), on channel slices; ragged pixel counts; ms as above."""
+    with _mfma_shape_pp128(ms):
+        _s2grad_case(variant)
+
+
+def _s2grad_case(variant):
     from adaptiveisp_amd.yolo import _lib
     L = _lib.load()
     st = _lib.stream_ptr()
