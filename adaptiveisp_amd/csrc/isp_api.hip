@@ -258,7 +258,8 @@ int adaisp_policy_finish(const adaisp_policy_finish_args* a, int B, void* stream
         !a->surrogate || !a->new_states || !a->penalty)
         return ADAISP_EINVAL;
     if (a->num_filters <= 0 || a->num_filters > ADAISP_POLICY_MAX_FILTERS || a->param_width <= 0 ||
-        a->param_width > ADAISP_MAX_PARAMS || a->hid <= 0 || a->num_rows <= 0 || B > 65535)
+        a->param_width > ADAISP_MAX_PARAMS || a->hid <= 0 || a->num_rows <= 0 || B > 65535 || a->noise_stride < 1 ||
+        a->forced_id >= a->num_filters)
         return ADAISP_ESHAPE;
     return launch_policy_finish(*a, B, static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }

@@ -350,9 +350,9 @@ typedef struct adaisp_policy_finish_args {
     float* new_states;         /* [B][3+F]                                                                      */
     float* penalty;            /* [B]                                                                           */
     /* scalars */
-    int32_t num_filters, num_rows, hid, param_width, noise_stride;
+    int32_t num_filters, num_rows, hid, param_width, noise_stride;      /* noise_stride >= 1                       */
     int32_t train_mode;        /* 1: pdf_sample, 0: argmax                                                      */
-    int32_t forced_id;         /* >= 0: teacher-forced selected_filter_id                                       */
+    int32_t forced_id;         /* >= 0: teacher-forced selected_filter_id, < num_filters                        */
     float one_minus_exploration, exploration_over_f;
     float entropy_coef;        /* (1 - progress) * cfg.exploration_penalty                                      */
     float log_num_filters, test_steps, filter_usage_penalty, early_stop_penalty, runtime_lambda;
@@ -546,7 +546,7 @@ int adaisp_clip_adam_step_dev(const adaisp_adam_tensor* table, int ntensors, lon
  * x [B][F][pw] = every fc_filter's output, zero in the slots >= n_f (what adaisp_policy_tail_fwd reads), logits [B][F]. Backward
  * (4 launches) from dx / dlogits: the gradient of every weight and bias into the caller's tensors (written, not accumulated) and of
  * both feature rows; `dhid` [B][F+1][hid] and `part` [(F+1)][B][D] are scratch. Every sum in a fixed order. B <= 8, hid a multiple of
- * 8, D a multiple of 1024.
+ * 8 and at most 256, D a multiple of 1024.
  */
 #define ADAISP_HEADS_MAX_B 8
 typedef struct adaisp_heads_args {
