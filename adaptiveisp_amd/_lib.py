@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_raw_load", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -76,6 +76,8 @@ def load():
     sz = ctypes.c_size_t
     L.adaisp_resize_u8.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, ci, ci, vp]
     L.adaisp_resize_u8.restype = ci
+    L.adaisp_raw_load.argtypes = [vp, sz, vp, vp, sz, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
+    L.adaisp_raw_load.restype = ci
     L.adaisp_export_u8.argtypes = [vp, vp, ci, ci, ci, vp]
     L.adaisp_export_u8.restype = ci
     L.adaisp_nlm_general.argtypes = [vp, vp, vp, ci, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, vp]
@@ -479,6 +481,51 @@ def resize_u8(src, dst, desc, tabs, records):
     _check(rc, "adaisp_resize_u8")
     _wrote(dst)
     return dst
+
+
+# adaisp_raw_desc (include/adaisp.h): one 64-byte record per plane
+RAW_DESC = np.dtype([("src_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"),
+                     ("left", "<i4"), ("tab_x", "<i8"), ("tab_y", "<i8"), ("gain", "<f4", (3,)), ("reserved", "<f4")],
+                    align=True)
+assert RAW_DESC.itemsize == 64
+
+
+def raw_load(src, desc, tabs, S, pattern="RGGB", method="bilinear", black_level=0.0, white_level=65535.0, out=None):
+    """adaisp_raw_load: native-size uint16 colour-filter-array planes packed in the device byte tensor `src` (even offsets;
+    a slice is fine) -> planar fp32 [B,3,S,S]: `demosaic_rects` of each whole plane (same `pattern`, `method`, levels),
+    times its gains, resampled through the CSR taps in `tabs` (adaptiveisp_amd/resize.py, RawTapPlan; a device int32 tensor
+    or 4-byte aligned bytes) and placed as `desc` (B records of RAW_DESC as a device byte tensor) says, 0 around it. Raises
+    on bad arguments before any device work."""
+    L, meth = load(), _method("raw_load", method)
+    for t, name in ((src, "src"), (desc, "desc"), (tabs, "tabs")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AdaispError(f"raw_load: {name} must be a HIP device tensor (there is no CPU path)")
+        if not t.is_contiguous():
+            raise AdaispError(f"raw_load: {name} must be contiguous")
+    for t, name in ((src, "src"), (desc, "desc")):
+        if t.dtype != torch.uint8:
+            raise AdaispError(f"raw_load: {name} must be a uint8 tensor, got {t.dtype}")
+    if src.data_ptr() % 2:
+        raise AdaispError("raw_load: src must be 2-byte aligned (uint16 samples)")
+    if desc.numel() % RAW_DESC.itemsize:
+        raise AdaispError(f"raw_load: desc holds {desc.numel()} bytes, not a whole number of {RAW_DESC.itemsize}-byte records")
+    if tabs.dtype not in (torch.uint8, torch.int32) or tabs.data_ptr() % 4 or (tabs.numel() * tabs.element_size()) % 4:
+        raise AdaispError("raw_load: tabs must be int32 words (an int32 tensor or 4-byte aligned bytes)")
+    if desc.device != src.device or tabs.device != src.device:
+        raise AdaispError(f"raw_load: src on {src.device}, desc on {desc.device}, tabs on {tabs.device}")
+    B, S = desc.numel() // RAW_DESC.itemsize, int(S)
+    if out is None:
+        out = torch.empty((B, 3, max(S, 1), max(S, 1)), dtype=torch.float32, device=src.device)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, 3, S, S) or out.dtype != torch.float32
+          or not out.is_contiguous() or out.device != src.device):
+        raise AdaispError(f"raw_load: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {src.device}")
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_raw_load(src.data_ptr(), src.numel(), desc.data_ptr(), tabs.data_ptr(),
+                               tabs.numel() * tabs.element_size() // 4, out.data_ptr(), B, S, _pattern(pattern), meth,
+                               float(black_level), float(white_level), _stream())
+    _check(rc, "adaisp_raw_load")
+    _wrote(out)
+    return out
 
 
 def export_u8(img, out=None):

@@ -13,18 +13,14 @@
 // staged in LDS as fp32 samples (34 x 130), then each lane produces 2x2 cells — two adjacent pixels per row, so every
 // plane is written with 8-byte stores, 512 contiguous bytes per wave and row.
 #include "isp_internal.h"
+#include "isp_demosaic_math.h"
 
 namespace adaisp {
 namespace {
 
 constexpr int TW = 128, TH = 32, LW = TW + 2, LH = TH + 2;
 
-// one reflection is all a valid output ever needs; the clamp only keeps the staging of rows / columns beyond the image
-// (tiles that overhang it) inside the allocation
-__device__ __forceinline__ int mirror(int i, int n) {
-    const int m = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
-    return min(max(m, 0), n - 1);
-}
+// mirror(), reflect2() and the per-site math: isp_demosaic_math.h (shared with isp_raw_load.hip)
 
 __global__ __launch_bounds__(256) void k_demosaic(const unsigned short* __restrict__ raw, float* __restrict__ out,
                                                   int H, int W, int ry, int rx, float black, float inv_range) {
@@ -54,14 +50,8 @@ __global__ __launch_bounds__(256) void k_demosaic(const unsigned short* __restri
                 const int ly = 2 * cy + dy + 1, lx = 2 * cx + dx + 1;
                 const float c = s[ly][lx];
                 const float n = s[ly - 1][lx], so = s[ly + 1][lx], w = s[ly][lx - 1], e = s[ly][lx + 1];
-                const float cross = ((n + so) + (w + e)) * 0.25f;
-                const float diag = ((s[ly - 1][lx - 1] + s[ly - 1][lx + 1]) + (s[ly + 1][lx - 1] + s[ly + 1][lx + 1])) * 0.25f;
-                const float horiz = (w + e) * 0.5f, vert = (n + so) * 0.5f;
-                const int py = (gy + dy - ry) & 1, px = (gx + dx - rx) & 1;      // 0,0 = red site; 1,1 = blue site
-                if (py == 0 && px == 0) { r[dx] = c; g[dx] = cross; bl[dx] = diag; }
-                else if (py == 0) { r[dx] = horiz; g[dx] = c; bl[dx] = vert; }
-                else if (px == 0) { r[dx] = vert; g[dx] = c; bl[dx] = horiz; }
-                else { r[dx] = diag; g[dx] = cross; bl[dx] = c; }
+                bilinear_site(c, n, so, w, e, s[ly - 1][lx - 1], s[ly - 1][lx + 1], s[ly + 1][lx - 1], s[ly + 1][lx + 1],
+                              (gy + dy - ry) & 1, (gx + dx - rx) & 1, r[dx], g[dx], bl[dx]);
             }
             const long off = (long)(gy + dy) * W + gx;
             *reinterpret_cast<float2*>(o + off) = make_float2(r[0], r[1]);
@@ -120,14 +110,8 @@ __global__ __launch_bounds__(256) void k_demosaic_rects(const unsigned short* __
                 const int ly = 2 * cy + dy + 1, lx = 2 * cx + dx + 1;
                 const float c = s[ly][lx];
                 const float n = s[ly - 1][lx], so = s[ly + 1][lx], we = s[ly][lx - 1], e = s[ly][lx + 1];
-                const float cross = ((n + so) + (we + e)) * 0.25f;
-                const float diag = ((s[ly - 1][lx - 1] + s[ly - 1][lx + 1]) + (s[ly + 1][lx - 1] + s[ly + 1][lx + 1])) * 0.25f;
-                const float horiz = (we + e) * 0.5f, vert = (n + so) * 0.5f;
-                const int py = (iy - ry) & 1, px = (ix - rx) & 1;                // 0,0 = red site; 1,1 = blue site
-                if (py == 0 && px == 0) { r[dx] = c; g[dx] = cross; bl[dx] = diag; }
-                else if (py == 0) { r[dx] = horiz; g[dx] = c; bl[dx] = vert; }
-                else if (px == 0) { r[dx] = vert; g[dx] = c; bl[dx] = horiz; }
-                else { r[dx] = diag; g[dx] = cross; bl[dx] = c; }
+                bilinear_site(c, n, so, we, e, s[ly - 1][lx - 1], s[ly - 1][lx + 1], s[ly + 1][lx - 1], s[ly + 1][lx + 1],
+                              (iy - ry) & 1, (ix - rx) & 1, r[dx], g[dx], bl[dx]);
             }
             if (gy + dy >= S) continue;                                          // odd S: the last cell row is half a cell
             const long off = (long)(gy + dy) * S + gx;
@@ -169,12 +153,6 @@ __global__ __launch_bounds__(256) void k_demosaic_rects(const unsigned short* __
 // per wave and row.
 constexpr int MR = 2, MLW = TW + 2 * MR, MLH = TH + 2 * MR;
 
-// np.pad(mode="reflect"), period 2n - 2, for every index a valid output reads: -2 <= i <= n + 1 with n >= 2. Two folds:
-// on a 2-pixel side -2 -> 2 -> 0 and 3 -> -1 -> 1; n >= 3 needs one. The clamp is for rows / columns further out, which
-// only the parts of a tile that overhang the image (or the rectangle) stage and nothing reads.
-__device__ __forceinline__ int fold(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-__device__ __forceinline__ int reflect2(int i, int n) { return min(max(fold(fold(i, n), n), 0), n - 1); }
-
 // One lane's 12 x 6 window: LDS rows 8 wave .. 8 wave + 11, columns 2 cx .. 2 cx + 5; pixel (8 wave + j, 2 cx + i) of the
 // tile is v[j + 2][i + 2].
 __device__ __forceinline__ void mhc_window(const float (&s)[MLH][MLW], int wave, int cx, float (&v)[12][6]) {
@@ -195,23 +173,7 @@ __device__ __forceinline__ void mhc_site(const float (&v)[12][6], int y, int x, 
     const float a1h = v[y][x - 1] + v[y][x + 1], a1v = v[y - 1][x] + v[y + 1][x];
     const float a2h = v[y][x - 2] + v[y][x + 2], a2v = v[y - 2][x] + v[y + 2][x];
     const float d = (v[y - 1][x - 1] + v[y - 1][x + 1]) + (v[y + 1][x - 1] + v[y + 1][x + 1]);
-    float ar, ag, ab;
-    if (py == px) {                                                              // red or blue site
-        const float own = 8.0f * c;
-        ag = 4.0f * c + 2.0f * (a1h + a1v) - (a2h + a2v);
-        const float opp = 6.0f * c + 2.0f * d - 1.5f * (a2h + a2v);
-        ar = py == 0 ? own : opp;
-        ab = py == 0 ? opp : own;
-    } else {                                                                     // green site
-        const float horiz = 5.0f * c + 4.0f * a1h - d - a2h + 0.5f * a2v;
-        const float vert = 5.0f * c + 4.0f * a1v - d - a2v + 0.5f * a2h;
-        ag = 8.0f * c;
-        ar = py == 0 ? horiz : vert;                                             // red row: red lies W / E
-        ab = py == 0 ? vert : horiz;
-    }
-    r = (ar * 0.125f) * inv_range;
-    g = (ag * 0.125f) * inv_range;
-    b = (ab * 0.125f) * inv_range;
+    mhc_site_sums(c, a1h, a1v, a2h, a2v, d, py, px, inv_range, r, g, b);
 }
 
 __global__ __launch_bounds__(256) void k_demosaic_mhc(const unsigned short* __restrict__ raw, float* __restrict__ out,

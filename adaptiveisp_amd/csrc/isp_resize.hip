@@ -18,6 +18,7 @@
 // it needs with byte loads, so images may start at any byte offset. The row's vertical taps are uniform across the
 // workgroup (scalar loads); a lane's horizontal taps are its own and stay in the L1 / L2 for the whole column.
 #include "isp_internal.h"
+#include "isp_csr.h"
 
 static_assert(sizeof(adaisp_resize_desc) == 56, "adaisp_resize_desc is 56 bytes (adaptiveisp_amd/_lib.py)");
 
@@ -27,33 +28,7 @@ namespace {
 constexpr int RS_THREADS = 256;
 constexpr int AREA_REG_TAPS = 16;   // horizontal AREA taps a lane keeps in registers (more: read from the table per row)
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 __device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)clampi(v, 0, 255); }
-
-// one CSR tap list of an AREA table: row `k` of `n` rows at word `base` of `tabs` (checked to fit by the caller)
-struct Csr {
-    const int32_t* idx;
-    const float* wt;
-    int lo, hi;
-};
-
-__device__ __forceinline__ Csr csr_row(const int32_t* __restrict__ tab, int n, int k) {
-    const int nnz = tab[n];
-    Csr r;
-    r.idx = tab + n + 1;
-    r.wt = reinterpret_cast<const float*>(tab + n + 1 + nnz);
-    r.lo = clampi(tab[k], 0, nnz);
-    r.hi = clampi(tab[k + 1], r.lo, nnz);
-    return r;
-}
-
-// an AREA table of n rows at word `base` lies inside tab_words (its nnz read only once the pointer array is known to fit)
-__device__ __forceinline__ bool csr_fits(const int32_t* __restrict__ tabs, int64_t base, int n, int64_t tab_words) {
-    if (base < 0 || base + n + 1 > tab_words) return false;
-    const int64_t nnz = tabs[base + n];
-    return nnz >= 0 && base + n + 1 + 2 * nnz <= tab_words;
-}
 
 __global__ __launch_bounds__(RS_THREADS) void k_resize_u8(const uint8_t* __restrict__ src, int64_t src_bytes,
                                                           uint8_t* __restrict__ dst, int64_t dst_bytes,

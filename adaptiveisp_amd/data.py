@@ -11,6 +11,10 @@ letterboxes on the device. The random draws of the metadata are the reference's,
 (`sample_unprocess_params`); the per-sample normals come from a counter-based generator on the device, so the noise is
 equal to the reference's in distribution, not in value.
 
+  `raw`   real captures (no counterpart in the reference, whose raw path starts from a synthesised plane): one 2-D uint16
+          .npy colour-filter-array plane per frame at the sensor's size. The plane crosses PCIe as it is (2 B/px) and one
+          adaisp_raw_load launch demosaics, applies per-channel gains, resamples to the letterbox size and places it.
+
 sensor="bayer" puts a simulated camera between the two: adaisp_unprocess_bayer keeps the one colour a Bayer filter passes
 at every pixel of the unprocessed (and, with add_noise, noisy) image and quantises it to a raw_bits plane, and
 adaisp_demosaic_rects interpolates the batch back from that plane, so the noise the policy sees is the demosaiced noise
@@ -23,7 +27,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .val.loader import imread_bgr, letterboxed_geometry, letterboxed_labels, list_images, load_letterboxed
+from .val.loader import (RAW_FORMATS, imread_bgr, letterboxed_geometry, letterboxed_labels, list_images, load_letterboxed,
+                         open_raw_plane)
 
 # random_ccm's XYZ -> camera matrices and the sRGB RGB -> XYZ matrix (isp/unprocess_np.py:5-35; Brooks et al.,
 # "Unprocessing Images for Learned Raw Denoising", CVPR 2019)
@@ -116,14 +121,25 @@ class ImageFolderSource:
     sensor="rgb": the same seed gives the same sensor parameters in both modes. HIP devices only; an image with a side
     under 2 pixels has no Bayer cell and raises ValueError.
 
-    On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` has no CPU path and raises."""
+    data_name="raw": the files are .npy, each one 2-D uint16 plane (anything else raises ValueError naming the file, and so
+    does a source without any .npy file), labels beside them as for images. Workers only open the file (np.load,
+    memory-mapped) and read the labels; the planes are copied from the mappings straight into the pinned slot (by the
+    workers, when there are any), each 16-byte aligned, behind the descriptors and tap tables of
+    adaptiveisp_amd/resize.RawTapPlan: one H2D copy, one adaisp_raw_load. The plane is resampled from its native size
+    straight to letterbox's un-padded size (h2, w2) of letterboxed_geometry (area weights when shrinking, fp32 bilinear
+    when enlarging): no second pass for load_image's ceil overshoot. Labels and `shapes` are those of a PNG of the same
+    size. `cfa`, `raw_bits`, `black_level`, `demosaic` mean what they mean for sensor="bayer"; `raw_gains` multiplies the
+    demosaiced R, G, B; `resize` is accepted and ignored (the resample is always on the device); the unprocess options
+    and sensor="bayer" raise ValueError. HIP devices only.
+
+    On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` and `raw` have no CPU path and raise."""
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
                  use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host", sensor="rgb", cfa="RGGB", raw_bits=12,
-                 black_level=None, demosaic="bilinear"):
+                 black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0)):
         from ._lib import CFA, DEMOSAIC
-        if data_name not in ("lod", "coco"):
-            raise ValueError(f"data_name must be 'lod' or 'coco', got {data_name!r}")
+        if data_name not in ("lod", "coco", "raw"):
+            raise ValueError(f"data_name must be 'lod', 'coco' or 'raw', got {data_name!r}")
         if resize not in ("host", "device"):
             raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
         if sensor not in ("rgb", "bayer"):
@@ -141,13 +157,22 @@ class ImageFolderSource:
             raise ValueError(f"black_level must be a whole number in [0, {self.white_level}), got {black_level!r}")
         self.black_level = int(self.black_level)
         self.device = torch.device(device)
+        self.raw_gains = tuple(float(v) for v in raw_gains)
+        if len(self.raw_gains) != 3 or not all(np.isfinite(self.raw_gains)):
+            raise ValueError(f"raw_gains must be three finite numbers (R, G, B), got {raw_gains!r}")
+        if data_name == "raw":
+            if sensor == "bayer":
+                raise ValueError("data_name='raw' with sensor='bayer': the plane already is a sensor's")
+            if add_noise or brightness_range is not None or noise_level is not None or use_linear:
+                raise ValueError("data_name='raw' takes the captures as they are: add_noise, brightness_range, noise_level "
+                                 "and use_linear belong to data_name='coco'")
         if sensor == "bayer" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(sensor='bayer'): the sensor and its demosaic run on the HIP device only "
                                "(adaisp_unprocess_bayer, adaisp_demosaic_rects_ex); there is no CPU path")
         if data_name == "coco" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(data_name='coco'): the unprocess runs on the HIP device only "
                                "(adaisp_unprocess); there is no CPU path")
-        if resize == "device" and self.device.type != "cuda":
+        if resize == "device" and self.device.type != "cuda" and data_name != "raw":
             raise RuntimeError("ImageFolderSource(resize='device'): the resample runs on the HIP device only "
                                "(adaisp_resize_u8); there is no CPU path")
         self.resize = resize
@@ -155,9 +180,22 @@ class ImageFolderSource:
             raise ValueError("add_noise needs data_name='coco'")
         if brightness_range is not None and isinstance(brightness_range, (list, tuple)):
             brightness_range = tuple(float(v) for v in brightness_range)
-        self.files = sorted(list_images(source))[rank::world]
+        if data_name == "raw":
+            try:
+                files = list_images(source, RAW_FORMATS)
+            except FileNotFoundError:
+                raise ValueError(f"{source}: data_name='raw' reads .npy planes and there is none") from None
+        else:
+            files = list_images(source)
+        self.files = sorted(files)[rank::world]
         if not self.files:
             raise FileNotFoundError(f"{source}: no images for rank {rank} of {world}")
+        if data_name == "raw":
+            for f in self.files:
+                open_raw_plane(f)                     # header only: a file that is no uint16 plane fails here, by name
+            if self.device.type != "cuda":
+                raise RuntimeError("ImageFolderSource(data_name='raw'): the demosaic and resample run on the HIP device only "
+                                   "(adaisp_raw_load); there is no CPU path")
         self.img_size, self.data_name = int(img_size), data_name
         self.add_noise, self.brightness_range = bool(add_noise), brightness_range
         self.noise_level, self.use_linear = noise_level, bool(use_linear)
@@ -183,6 +221,10 @@ class ImageFolderSource:
             self._pool = None
 
     def describe(self):
+        if self.data_name == "raw":
+            gains = "" if self.raw_gains == (1.0, 1.0, 1.0) else ", gains " + " ".join(f"{g:g}" for g in self.raw_gains)
+            return (f"raw ({self.cfa} {self.raw_bits}-bit black {self.black_level}, {self.demosaic} demosaic{gains}): "
+                    f"{len(self.files)} files")
         kind = "coco (unprocess" + (", noise" if self.add_noise else "") + ")" if self.data_name == "coco" else "lod"
         bayer = f", bayer {self.cfa} {self.raw_bits}-bit black {self.black_level}" if self.sensor == "bayer" else ""
         if bayer and self.demosaic != "bilinear":
@@ -203,6 +245,14 @@ class ImageFolderSource:
         ((h, w) after load_image, (h2, w2) after letterbox's resize) says what the device makes of it; otherwise `im` is
         load_letterboxed's and `sizes` None."""
         path = self.files[i]
+        if self.data_name == "raw":
+            plane = open_raw_plane(path)
+            size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(plane.shape[0], plane.shape[1],
+                                                                                       self.img_size)
+            lb = letterboxed_labels(path, size, frame, ratio, pad)
+            label = np.zeros((len(lb), 6), np.float32)
+            label[:, 1:] = lb
+            return plane, top, left, label, path, shapes, unpad
         if self.resize == "device":
             im = imread_bgr(path)
             size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(im.shape[0], im.shape[1],
@@ -280,8 +330,57 @@ class ImageFolderSource:
         lay = dict(rec1=rec1, rec2=rec2, tab=tab, r1=r1, r2=r2, tb=tb, base=base, s1=off1, s2=off2)
         return lay, final
 
+    def _raw_batch(self, items):
+        """data_name="raw": one pinned buffer (descriptors, tap tables, the planes, each 16-byte aligned), one H2D copy, one
+        adaisp_raw_load on the current stream."""
+        from . import _lib
+        from .resize import RawTapPlan
+        S, B = self.img_size, len(items)
+        plan, at, pos = RawTapPlan(), [], 0
+        for plane, top, left, _lb, path, _shapes, unpad in items:
+            if min(plane.shape) < 2:
+                raise ValueError(f"{path}: {plane.shape[0]} x {plane.shape[1]} samples: a raw plane needs at least 2 x 2")
+            plan.add(plane.shape, unpad, (top, left), pos, self.raw_gains)
+            at.append(pos)
+            pos = (pos + plane.nbytes + 15) // 16 * 16
+        self.serial += B
+        desc, tab = plan.descriptors(), plan.table()
+        dbytes = (desc.nbytes + 15) // 16 * 16
+        base = dbytes + (tab.nbytes + 15) // 16 * 16
+        total = base + pos
+        slot = self._slots[self._slot]
+        self._slot = (self._slot + 1) % len(self._slots)
+        if slot["event"] is not None:
+            slot["event"].synchronize()           # this slot's previous H2D copy has finished reading it
+        if slot["host"] is None or slot["host"].numel() < total:
+            slot["host"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host = slot["host"].numpy()
+        host[:desc.nbytes] = desc.view(np.uint8)
+        host[dbytes:dbytes + tab.nbytes] = tab.view(np.uint8)
+
+        def copy(k):                              # the one host pass over the samples: mapping -> pinned slot
+            plane = items[k][0]
+            host[base + at[k]:base + at[k] + plane.nbytes].view(np.uint16).reshape(plane.shape)[...] = plane
+
+        if self._pool is not None:
+            list(self._pool.map(copy, range(B)))
+        else:
+            for k in range(B):
+                copy(k)
+        with torch.cuda.device(self.device):
+            if self._dev is None or self._dev.numel() < total:
+                self._dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+            self._dev[:total].copy_(slot["host"][:total], non_blocking=True)
+            slot["event"] = torch.cuda.Event()
+            slot["event"].record()
+            return _lib.raw_load(self._dev[base:total], self._dev[:desc.nbytes], self._dev[dbytes:dbytes + tab.nbytes], S,
+                                 pattern=self.cfa, method=self.demosaic, black_level=self.black_level,
+                                 white_level=self.white_level)
+
     def _device_batch(self, items):
         from . import _lib
+        if self.data_name == "raw":
+            return self._raw_batch(items)
         S, B = self.img_size, len(items)
         desc = np.zeros(B, _lib.UNPROCESS_DESC)
         dbytes = (B * _lib.UNPROCESS_DESC.itemsize + 15) // 16 * 16

@@ -381,11 +381,12 @@ class _GraphIteration:
 def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epochs=800, save_dir=None, sync_bn=False,
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
                   add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host",
-                  sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear"):
+                  sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0)):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
-    reference's unprocess options; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
+    reference's unprocess options, or "raw": uint16 .npy sensor planes with `cfa` / `raw_bits` / `black_level` / `demosaic`
+    / `raw_gains`; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
     where the resample to the training size runs; `sensor` "bayer": through the simulated `cfa` / `raw_bits` /
     `black_level` sensor and its `demosaic`, "bilinear" or "mhc"); None: SyntheticSource."""
     import random
@@ -423,7 +424,8 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
         source = ImageFolderSource(data, H, device, data_name=data_name, add_noise=add_noise,
                                    brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
                                    seed=seed, rank=rank, world=world, workers=workers, resize=resize,
-                                   sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level, demosaic=demosaic)
+                                   sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level, demosaic=demosaic,
+                                   raw_gains=raw_gains)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -446,8 +448,12 @@ def build_parser():
     ap.add_argument("--isp-ckpt", default=None, help="ckpt-*.pth to resume from")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--data", default=None, help="image directory or .txt list to train on (default: synthetic images)")
-    ap.add_argument("--data-name", default="lod", choices=("lod", "coco"),
-                    help="lod: images / 255; coco: sRGB -> synthetic low-light linear RGB (unprocess_wo_mosaic)")
+    ap.add_argument("--data-name", default="lod", choices=("lod", "coco", "raw"),
+                    help="lod: images / 255; coco: sRGB -> synthetic low-light linear RGB (unprocess_wo_mosaic); raw: real "
+                         "captures, one 2-D uint16 .npy colour-filter-array plane per frame at the sensor's size, demosaiced "
+                         "(--cfa, --raw-bits, --black-level, --demosaic) and resampled to --size in one HIP launch")
+    ap.add_argument("--raw-gains", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("R", "G", "B"),
+                    help="raw: per-channel multipliers on the demosaiced values (white balance)")
     ap.add_argument("--add-noise", action="store_true", help="coco: shot + read noise")
     ap.add_argument("--bri-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="coco: random brightness ratio in [LO, HI)")
@@ -470,12 +476,24 @@ def build_parser():
     return ap
 
 
+def parse_args(argv=None):
+    """Parsed and checked arguments; a usage error exits with status 2 before anything touches a device."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.data_name == "raw" and a.sensor == "bayer":
+        ap.error("--data-name raw with --sensor bayer: the planes already are a sensor's")
+    if a.data_name == "raw" and (a.add_noise or a.bri_range is not None):
+        print("note: --data-name raw trains on the captures as they are: --add-noise / --bri-range ignored")
+        a.add_noise, a.bri_range = False, None
+    return a
+
+
 def main(argv=None):
     import json
     import time
 
     from .config import cfg
-    a = build_parser().parse_args(argv)
+    a = parse_args(argv)
     if a.gpus and a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import sys
         # the parent never touches the GPU: it starts the ranks as a child and exits with their code
@@ -511,7 +529,8 @@ def main(argv=None):
                            sync_bn=a.sync_bn, detector_ckpt=a.detector_ckpt, isp_ckpt=a.isp_ckpt, seed=a.seed, tune_cache=cache,
                            data=a.data, data_name=a.data_name, add_noise=a.add_noise, brightness_range=a.bri_range,
                            noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers, resize=a.resize,
-                           sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic)
+                           sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic,
+                           raw_gains=tuple(a.raw_gains))
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

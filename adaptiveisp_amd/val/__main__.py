@@ -80,8 +80,12 @@ def build_parser():
     ap.add_argument("--detector-ckpt", default=None, help="yolov3.pt (default: a random-init YOLOv3, for smoke runs only)")
     ap.add_argument("--data", required=True, help="dataset YAML, or an image directory / .txt list / image")
     ap.add_argument("--task", default="val", choices=("val", "test", "train"), help="which YAML entry to evaluate")
-    ap.add_argument("--data-name", default="lod", choices=("lod", "coco"),
-                    help="lod: images / 255; coco: sRGB -> synthetic low-light linear RGB (unprocess_wo_mosaic)")
+    ap.add_argument("--data-name", default="lod", choices=("lod", "coco", "raw"),
+                    help="lod: images / 255; coco: sRGB -> synthetic low-light linear RGB (unprocess_wo_mosaic); raw: real "
+                         "captures, one 2-D uint16 .npy colour-filter-array plane per frame at the sensor's size, demosaiced "
+                         "(--cfa, --raw-bits, --black-level, --demosaic) and resampled to --img-size in one HIP launch")
+    ap.add_argument("--raw-gains", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("R", "G", "B"),
+                    help="raw: per-channel multipliers on the demosaiced values (white balance)")
     ap.add_argument("--add-noise", action="store_true", help="coco: shot + read noise")
     ap.add_argument("--bri-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="coco: random brightness ratio in [LO, HI)")
@@ -152,9 +156,11 @@ def parse_args(argv=None):
             ap.error(f"--pipeline ids {bad} outside [0, {len(cfg.filters)})")
     if a.save_param and a.batch_size != 1:
         ap.error(f"--save-param needs --batch-size 1 (got {a.batch_size})")
-    if a.data_name == "lod" and (a.add_noise or a.bri_range is not None):
-        print("note: --data-name lod evaluates the images as they are: --add-noise / --bri-range ignored")
-    if a.data_name == "lod":
+    if a.data_name == "raw" and a.sensor == "bayer":
+        ap.error("--data-name raw with --sensor bayer: the planes already are a sensor's")
+    if a.data_name in ("lod", "raw") and (a.add_noise or a.bri_range is not None):
+        print(f"note: --data-name {a.data_name} evaluates the images as they are: --add-noise / --bri-range ignored")
+    if a.data_name in ("lod", "raw"):
         a.add_noise, a.bri_range = False, None
     a.img_size = check_img_size(a.img_size)
     if a.graph and (a.save_image or a.save_param):
@@ -237,7 +243,8 @@ def main(argv=None):
     src = ImageFolderSource(source, a.img_size, dev, data_name=a.data_name, add_noise=a.add_noise,
                             brightness_range=a.bri_range, noise_level=a.noise_level, use_linear=a.use_linear,
                             seed=a.seed, workers=a.workers, resize=a.resize, sensor=a.sensor, cfa=a.cfa,
-                            raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic)
+                            raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic,
+                            raw_gains=tuple(a.raw_gains))
     n_files = len(src)
     engines = {}
     for b in {min(a.batch_size, n_files), n_files % a.batch_size or a.batch_size}:

@@ -187,9 +187,12 @@ def load_letterboxed(path, img_size):
     return np.ascontiguousarray(im), place, frame, letterboxed_labels(path, size, frame, ratio, pad), shapes
 
 
-def list_images(source):
-    """A directory (recursive), a .txt list (`./` entries relative to it) or a list of paths -> the image files, in the
-    order given (directories: sorted)."""
+RAW_FORMATS = ("npy",)              # raw captures: one 2-D uint16 colour-filter-array plane per file
+
+
+def list_images(source, formats=IMG_FORMATS):
+    """A directory (recursive), a .txt list (`./` entries relative to it) or a list of paths -> the image files (those
+    with an extension in `formats`), in the order given (directories: sorted)."""
     if isinstance(source, (list, tuple)):
         files = list(source)
     elif os.path.isdir(source):
@@ -198,10 +201,23 @@ def list_images(source):
         base = os.path.dirname(source)
         files = [ln.strip() for ln in open(source) if ln.strip()]
         files = [os.path.join(base, f[2:]) if f.startswith("./") else f for f in files]
-    files = [f for f in files if f.rsplit(".", 1)[-1].lower() in IMG_FORMATS]
+    files = [f for f in files if f.rsplit(".", 1)[-1].lower() in formats]
     if not files:
         raise FileNotFoundError(f"no images under {source}")
     return files
+
+
+def open_raw_plane(path):
+    """A raw capture: the 2-D uint16 array of a .npy file, memory-mapped (nothing is read until it is copied). Anything
+    else raises ValueError naming the file."""
+    try:
+        plane = np.load(path, mmap_mode="r", allow_pickle=False)
+    except Exception as e:                               # not a .npy file, or one that holds objects
+        raise ValueError(f"{path}: not a .npy array ({e})") from None
+    if not isinstance(plane, np.ndarray) or plane.dtype != np.uint16 or plane.ndim != 2:
+        raise ValueError(f"{path}: a raw capture is one 2-D uint16 array, got {getattr(plane, 'dtype', type(plane))} "
+                         f"{getattr(plane, 'shape', '')}")
+    return plane
 
 
 class LODImages:

@@ -275,6 +275,44 @@ int adaisp_resize_u8(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t 
                      void* stream);
 
 /*
+ * Raw-capture loader: real sensor planes -> the letterboxed [B,3,S,S] fp32 batch in one launch (demosaic, per-channel gain,
+ * resample, placement). The plane is read once, 2 bytes per native pixel, and only the batch is written: the full-resolution
+ * colour image never exists in memory.
+ * src: uint16 [src_h, src_w] colour-filter-array planes, row-major, packed at any EVEN byte offsets (src itself 2-byte
+ * aligned). desc: a DEVICE array of B records. For image b, with pattern / method / black_level / white_level as
+ * adaisp_demosaic_rects_ex:
+ *   demosaic   D_c(j, i) = what adaisp_demosaic_rects_ex gives for a rectangle that is the whole plane at origin (0, 0), bit
+ *              for bit: CFA phase relative to the plane's first sample, mirrors at the plane's edges, odd sides allowed (the
+ *              crop continued by its mirror), nothing clamped
+ *   gain       V_c(j, i) = D_c(j, i) * gain[c]                                   (one fp32 multiply)
+ *   resample   taps in `tabs` (32-bit words, floats by their bits), CSR in adaisp_resize_u8's AREA layout:
+ *              at tab_x: ptr[w + 1], idx[nnz], weight[nnz] (src_w -> w), at tab_y the same over h (src_h -> h); the host builds
+ *              them (adaptiveisp_amd/resize.py, raw_table: the area weights when shrinking, two-tap fp32 bilinear when
+ *              enlarging, one tap of weight 1 when equal). Horizontal pass, then vertical pass, each a sequence of one fp32
+ *              multiply then one fp32 add in tap order, starting from 0.0f (no FMA):
+ *                  T_c(j, x):    t = t + wx * V_c(j, idx)      over the taps of x
+ *                  out_c(y, x):  acc = acc + wy * T_c(idx, x)  over the taps of y
+ *              source indices read from the taps are clamped to the plane
+ *   placement  the h x w result at (top, left) of out[b]; every other sample of out[b] is exactly 0
+ * out[b] is all zero when the placement does not fit the frame, src_h < 2 or src_w < 2, the plane does not lie inside
+ * src_bytes, the taps do not lie inside tab_words, or src_offset is odd. Every byte of out is written by every call.
+ * ADAISP_EINVAL: null pointers, an odd src, B < 0, S < 1, unknown pattern or method, white_level <= black_level;
+ * ADAISP_ESHAPE: B > 65535 or S > 32768; B == 0 is ok and launches nothing; all checked before anything touches a device.
+ * No allocation, no host synchronisation: capturable in a hipGraph.
+ */
+typedef struct adaisp_raw_desc {
+    int64_t src_offset;        /* byte offset of the plane's first sample in src (even)                          */
+    int32_t src_h, src_w;      /* native plane size; each >= 2, any parity                                       */
+    int32_t h, w, top, left;   /* resampled size and its placement in the S x S frame                            */
+    int64_t tab_x, tab_y;      /* word offsets in tabs of the horizontal (src_w -> w) / vertical taps            */
+    float   gain[3];           /* R, G, B multipliers applied to the demosaiced values (1 = none)                */
+    float   reserved;
+} adaisp_raw_desc;
+int adaisp_raw_load(const uint8_t* src, size_t src_bytes, const adaisp_raw_desc* desc, const int32_t* tabs,
+                    size_t tab_words, float* out, int B, int S, int pattern, int method, float black_level,
+                    float white_level, void* stream);
+
+/*
  * Image export: planar fp32 RGB img [B,3,H,W] -> interleaved uint8 BGR out [B,H,W,3] (cv2.imwrite's channel order), in one
  * launch, with the arithmetic of the reference's `save_img` (util.py:21-40) and OpenCV's float -> 8U conversion:
  * NaN -> 0, clip to [0, 1], * 255.0f in fp32, round half to even. Any pointer alignment (16-byte loads where the
