@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_raw_load", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_raw_load", "adaisp_raw_correct", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -78,6 +78,8 @@ def load():
     L.adaisp_resize_u8.restype = ci
     L.adaisp_raw_load.argtypes = [vp, sz, vp, vp, sz, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
     L.adaisp_raw_load.restype = ci
+    L.adaisp_raw_correct.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, vp]
+    L.adaisp_raw_correct.restype = ci
     L.adaisp_export_u8.argtypes = [vp, vp, ci, ci, ci, vp]
     L.adaisp_export_u8.restype = ci
     L.adaisp_nlm_general.argtypes = [vp, vp, vp, ci, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, vp]
@@ -524,6 +526,53 @@ def raw_load(src, desc, tabs, S, pattern="RGGB", method="bilinear", black_level=
                                tabs.numel() * tabs.element_size() // 4, out.data_ptr(), B, S, _pattern(pattern), meth,
                                float(black_level), float(white_level), _stream())
     _check(rc, "adaisp_raw_load")
+    _wrote(out)
+    return out
+
+
+# adaisp_rawfix_desc (include/adaisp.h): one 96-byte record per plane
+RAWFIX_DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("grid", "<i8"),
+                        ("grid_h", "<i4"), ("grid_w", "<i4"), ("step_y", "<f4"), ("step_x", "<f4"), ("black", "<f4", (4,)),
+                        ("scale", "<f4", (4,)), ("black_out", "<f4"), ("dpc", "<i4"), ("reserved", "<i4", (2,))], align=True)
+assert RAWFIX_DESC.itemsize == 96
+
+
+def raw_correct(src, desc, gains=None, out=None):
+    """adaisp_raw_correct: the uint16 colour-filter-array planes packed in the device byte tensor `src` (even offsets; a
+    slice is fine) -> corrected uint16 planes in the device byte tensor `out` (default: a new one of src's size), each as
+    its record of `desc` (B records of RAWFIX_DESC as a device byte tensor; adaptiveisp_amd/rawcal.py fills them) says:
+    defect pixels, shading gain from the tables in `gains` (a device float32 tensor, or None when no record has one),
+    per-position black levels and scale. `out` must not overlap `src`. Raises on bad arguments before any device work."""
+    L = load()
+    named = ((src, "src"), (desc, "desc")) + (() if out is None else ((out, "out"),)) + (() if gains is None else ((gains, "gains"),))
+    for t, name in named:
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AdaispError(f"raw_correct: {name} must be a HIP device tensor (there is no CPU path)")
+        if not t.is_contiguous():
+            raise AdaispError(f"raw_correct: {name} must be contiguous")
+        if t.device != src.device:
+            raise AdaispError(f"raw_correct: src on {src.device}, {name} on {t.device}")
+        if name != "gains" and t.dtype != torch.uint8:
+            raise AdaispError(f"raw_correct: {name} must be a uint8 tensor, got {t.dtype}")
+    if gains is not None and gains.dtype != torch.float32:
+        raise AdaispError(f"raw_correct: gains must be a float32 tensor, got {gains.dtype}")
+    if desc.numel() % RAWFIX_DESC.itemsize:
+        raise AdaispError(f"raw_correct: desc holds {desc.numel()} bytes, not a whole number of {RAWFIX_DESC.itemsize}-byte "
+                          "records")
+    B = desc.numel() // RAWFIX_DESC.itemsize
+    if B > 65535:
+        raise AdaispError(f"raw_correct: {B} records, at most 65535 per launch")
+    if out is None:
+        out = torch.empty(src.numel(), dtype=torch.uint8, device=src.device)
+    if src.data_ptr() % 2 or out.data_ptr() % 2:
+        raise AdaispError("raw_correct: src and out must be 2-byte aligned (uint16 samples)")
+    if src.data_ptr() < out.data_ptr() + out.numel() and out.data_ptr() < src.data_ptr() + src.numel():
+        raise AdaispError("raw_correct: out overlaps src (the defect rule reads neighbours: not in place)")
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_raw_correct(src.data_ptr(), src.numel(), out.data_ptr(), out.numel(), desc.data_ptr(),
+                                  None if gains is None else gains.data_ptr(), 0 if gains is None else gains.numel(), B,
+                                  _stream())
+    _check(rc, "adaisp_raw_correct")
     _wrote(out)
     return out
 

@@ -20,6 +20,7 @@ at every pixel of the unprocessed (and, with add_noise, noisy) image and quantis
 adaisp_demosaic_rects interpolates the batch back from that plane, so the noise the policy sees is the demosaiced noise
 of a raw sensor rather than white noise per channel (the reference's `unprocess` + `mosaic`, isp/unprocess_np.py:217-245).
 """
+import os
 import random
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
@@ -131,13 +132,20 @@ class ImageFolderSource:
     size. `cfa`, `raw_bits`, `black_level`, `demosaic` mean what they mean for sensor="bayer"; `raw_gains` multiplies the
     demosaiced R, G, B; `resize` is accepted and ignored (the resample is always on the device); the unprocess options
     and sensor="bayer" raise ValueError. HIP devices only.
+    `raw_calibration` (a rawcal.RawCalibration or the path of one) and `raw_meta` (read <stem>.json beside <stem>.npy when
+    the folder is opened: black_level, white_level, gains; a malformed one raises ValueError naming it) are for real
+    sensors: with either, adaisp_raw_correct runs before adaisp_raw_load, in a launch of its own over the batch: defect
+    pixels, lens shading, per-position black levels, every capture's levels (its sidecar's, else the calibration's, else the
+    run's) brought to the run's black_level and white level; a sidecar's gains replace `raw_gains` for that capture.
+    Without both, nothing changes: no extra launch, no extra bytes. They raise ValueError with another data_name.
 
     On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` and `raw` have no CPU path and raise."""
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
                  use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host", sensor="rgb", cfa="RGGB", raw_bits=12,
-                 black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0)):
+                 black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0), raw_calibration=None, raw_meta=False):
         from ._lib import CFA, DEMOSAIC
+        from .rawcal import RawCalibration, read_sidecar, resolve
         if data_name not in ("lod", "coco", "raw"):
             raise ValueError(f"data_name must be 'lod', 'coco' or 'raw', got {data_name!r}")
         if resize not in ("host", "device"):
@@ -166,6 +174,15 @@ class ImageFolderSource:
             if add_noise or brightness_range is not None or noise_level is not None or use_linear:
                 raise ValueError("data_name='raw' takes the captures as they are: add_noise, brightness_range, noise_level "
                                  "and use_linear belong to data_name='coco'")
+        if data_name != "raw" and (raw_calibration is not None or raw_meta):
+            raise ValueError("raw_calibration and raw_meta belong to data_name='raw'")
+        if isinstance(raw_calibration, (str, os.PathLike)):
+            raw_calibration = RawCalibration.load(raw_calibration)
+        if raw_calibration is not None and not isinstance(raw_calibration, RawCalibration):
+            raise ValueError(f"raw_calibration must be a RawCalibration or the path of one, got {type(raw_calibration).__name__}")
+        if raw_calibration is not None and raw_calibration.cfa != self.cfa:
+            raise ValueError(f"raw_calibration is of a {raw_calibration.cfa} sensor, cfa is {self.cfa}")
+        self.raw_calibration, self.raw_meta = raw_calibration, bool(raw_meta)
         if sensor == "bayer" and self.device.type != "cuda":
             raise RuntimeError("ImageFolderSource(sensor='bayer'): the sensor and its demosaic run on the HIP device only "
                                "(adaisp_unprocess_bayer, adaisp_demosaic_rects_ex); there is no CPU path")
@@ -193,6 +210,12 @@ class ImageFolderSource:
         if data_name == "raw":
             for f in self.files:
                 open_raw_plane(f)                     # header only: a file that is no uint16 plane fails here, by name
+            # sidecars are read here, once: a malformed one fails by name; levels that cannot be used fail by name too
+            self._meta = {f: read_sidecar(f) for f in self.files} if self.raw_meta else {}
+            for f in self.files:
+                resolve(self.raw_calibration, self._meta.get(f), self.black_level, self.white_level,
+                        where=f if self._meta.get(f) else "raw_calibration")
+            self._rawfix = self.raw_calibration is not None or any(m is not None for m in self._meta.values())
             if self.device.type != "cuda":
                 raise RuntimeError("ImageFolderSource(data_name='raw'): the demosaic and resample run on the HIP device only "
                                    "(adaisp_raw_load); there is no CPU path")
@@ -211,6 +234,8 @@ class ImageFolderSource:
         self._slot = 0
         self._dev = None
         self._plane = None                        # sensor="bayer": the uint16 plane between the two kernels
+        if data_name != "raw":
+            self._meta, self._rawfix = {}, False
 
     def __len__(self):
         return len(self.files)
@@ -223,7 +248,10 @@ class ImageFolderSource:
     def describe(self):
         if self.data_name == "raw":
             gains = "" if self.raw_gains == (1.0, 1.0, 1.0) else ", gains " + " ".join(f"{g:g}" for g in self.raw_gains)
-            return (f"raw ({self.cfa} {self.raw_bits}-bit black {self.black_level}, {self.demosaic} demosaic{gains}): "
+            cal = "" if self.raw_calibration is None else f", calibration {self.raw_calibration.describe()}"
+            if self.raw_meta:
+                cal += f", {sum(m is not None for m in self._meta.values())} sidecars"
+            return (f"raw ({self.cfa} {self.raw_bits}-bit black {self.black_level}, {self.demosaic} demosaic{gains}{cal}): "
                     f"{len(self.files)} files")
         kind = "coco (unprocess" + (", noise" if self.add_noise else "") + ")" if self.data_name == "coco" else "lod"
         bayer = f", bayer {self.cfa} {self.raw_bits}-bit black {self.black_level}" if self.sensor == "bayer" else ""
@@ -332,21 +360,39 @@ class ImageFolderSource:
 
     def _raw_batch(self, items):
         """data_name="raw": one pinned buffer (descriptors, tap tables, the planes, each 16-byte aligned), one H2D copy, one
-        adaisp_raw_load on the current stream."""
+        adaisp_raw_load on the current stream. With a calibration or sidecars in play the adaisp_raw_correct descriptors
+        and the shading table ride in the same buffer between the tap tables and the planes, the device buffer has a
+        second plane region behind the first, adaisp_raw_correct runs from the first into the second (every capture with
+        its own levels, brought to the run's black and white level) and adaisp_raw_load reads the second."""
         from . import _lib
+        from .rawcal import fill_rawfix, level_scale, resolve
         from .resize import RawTapPlan
         S, B = self.img_size, len(items)
         plan, at, pos = RawTapPlan(), [], 0
         for plane, top, left, _lb, path, _shapes, unpad in items:
             if min(plane.shape) < 2:
                 raise ValueError(f"{path}: {plane.shape[0]} x {plane.shape[1]} samples: a raw plane needs at least 2 x 2")
-            plan.add(plane.shape, unpad, (top, left), pos, self.raw_gains)
+            meta = self._meta.get(path) or {}
+            plan.add(plane.shape, unpad, (top, left), pos, meta.get("gains", self.raw_gains))
             at.append(pos)
             pos = (pos + plane.nbytes + 15) // 16 * 16
         self.serial += B
         desc, tab = plan.descriptors(), plan.table()
         dbytes = (desc.nbytes + 15) // 16 * 16
         base = dbytes + (tab.nbytes + 15) // 16 * 16
+        fix = shading = None
+        if self._rawfix:
+            cal = self.raw_calibration
+            shading = None if cal is None else cal.shading
+            fix = np.zeros(B, _lib.RAWFIX_DESC)
+            for k, (plane, _t, _l, _lb, path, *_rest) in enumerate(items):
+                black, white = resolve(cal, self._meta.get(path), self.black_level, self.white_level, where=path)
+                fill_rawfix(fix[k], plane.shape, at[k], at[k], black,
+                            level_scale(black, white, self.black_level, self.white_level), self.black_level,
+                            None if cal is None else cal.dpc, None if shading is None else (0, *shading.shape[1:]))
+            fbase = base
+            gbase = fbase + (fix.nbytes + 15) // 16 * 16
+            base = gbase + ((0 if shading is None else shading.nbytes) + 15) // 16 * 16
         total = base + pos
         slot = self._slots[self._slot]
         self._slot = (self._slot + 1) % len(self._slots)
@@ -357,6 +403,10 @@ class ImageFolderSource:
         host = slot["host"].numpy()
         host[:desc.nbytes] = desc.view(np.uint8)
         host[dbytes:dbytes + tab.nbytes] = tab.view(np.uint8)
+        if fix is not None:
+            host[fbase:fbase + fix.nbytes] = fix.view(np.uint8)
+            if shading is not None:
+                host[gbase:gbase + shading.nbytes] = shading.reshape(-1).view(np.uint8)
 
         def copy(k):                              # the one host pass over the samples: mapping -> pinned slot
             plane = items[k][0]
@@ -368,12 +418,17 @@ class ImageFolderSource:
             for k in range(B):
                 copy(k)
         with torch.cuda.device(self.device):
-            if self._dev is None or self._dev.numel() < total:
-                self._dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+            need = total + (pos if fix is not None else 0)
+            if self._dev is None or self._dev.numel() < need:
+                self._dev = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._dev[:total].copy_(slot["host"][:total], non_blocking=True)
             slot["event"] = torch.cuda.Event()
             slot["event"].record()
-            return _lib.raw_load(self._dev[base:total], self._dev[:desc.nbytes], self._dev[dbytes:dbytes + tab.nbytes], S,
+            planes = self._dev[base:total]
+            if fix is not None:
+                gains = None if shading is None else self._dev[gbase:gbase + shading.nbytes].view(torch.float32)
+                planes = _lib.raw_correct(planes, self._dev[fbase:fbase + fix.nbytes], gains, out=self._dev[total:total + pos])
+            return _lib.raw_load(planes, self._dev[:desc.nbytes], self._dev[dbytes:dbytes + tab.nbytes], S,
                                  pattern=self.cfa, method=self.demosaic, black_level=self.black_level,
                                  white_level=self.white_level)
 

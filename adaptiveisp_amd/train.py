@@ -15,6 +15,7 @@ import os
 import torch
 
 from . import dist as adist
+from .rawcal import calibration_from_options
 from .rl import lr_lambda, train_iteration
 from .yolo.checkpoint import save_isp_checkpoint
 
@@ -381,12 +382,13 @@ class _GraphIteration:
 def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epochs=800, save_dir=None, sync_bn=False,
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
                   add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host",
-                  sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0)):
+                  sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0),
+                  raw_calibration=None, raw_meta=False):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
     reference's unprocess options, or "raw": uint16 .npy sensor planes with `cfa` / `raw_bits` / `black_level` / `demosaic`
-    / `raw_gains`; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
+    / `raw_gains` / `raw_calibration` / `raw_meta`; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
     where the resample to the training size runs; `sensor` "bayer": through the simulated `cfa` / `raw_bits` /
     `black_level` sensor and its `demosaic`, "bilinear" or "mhc"); None: SyntheticSource."""
     import random
@@ -425,7 +427,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                                    brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
                                    seed=seed, rank=rank, world=world, workers=workers, resize=resize,
                                    sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level, demosaic=demosaic,
-                                   raw_gains=raw_gains)
+                                   raw_gains=raw_gains, raw_calibration=raw_calibration, raw_meta=raw_meta)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -454,6 +456,13 @@ def build_parser():
                          "(--cfa, --raw-bits, --black-level, --demosaic) and resampled to --size in one HIP launch")
     ap.add_argument("--raw-gains", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("R", "G", "B"),
                     help="raw: per-channel multipliers on the demosaiced values (white balance)")
+    ap.add_argument("--raw-cal", default=None, metavar="FILE",
+                    help="raw: sensor calibration (.npz of python -m adaptiveisp_amd.rawcal): per-position black levels, "
+                         "white level, lens shading, defect threshold, applied in one HIP launch before the demosaic")
+    ap.add_argument("--raw-dpc", type=int, default=None, metavar="N",
+                    help="raw: defect-pixel threshold in sensor counts (overrides the calibration's; alone: defects only)")
+    ap.add_argument("--raw-meta", action="store_true",
+                    help="raw: read <stem>.json beside each plane: black_level, white_level, gains (as-shot R G B)")
     ap.add_argument("--add-noise", action="store_true", help="coco: shot + read noise")
     ap.add_argument("--bri-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="coco: random brightness ratio in [LO, HI)")
@@ -482,6 +491,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.data_name == "raw" and a.sensor == "bayer":
         ap.error("--data-name raw with --sensor bayer: the planes already are a sensor's")
+    if a.data_name != "raw" and (a.raw_cal is not None or a.raw_dpc is not None or a.raw_meta):
+        ap.error("--raw-cal / --raw-dpc / --raw-meta need --data-name raw")
+    if a.raw_dpc is not None and a.raw_dpc < 0:
+        ap.error(f"--raw-dpc must be >= 0 (got {a.raw_dpc})")
     if a.data_name == "raw" and (a.add_noise or a.bri_range is not None):
         print("note: --data-name raw trains on the captures as they are: --add-noise / --bri-range ignored")
         a.add_noise, a.bri_range = False, None
@@ -530,7 +543,8 @@ def main(argv=None):
                            data=a.data, data_name=a.data_name, add_noise=a.add_noise, brightness_range=a.bri_range,
                            noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers, resize=a.resize,
                            sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic,
-                           raw_gains=tuple(a.raw_gains))
+                           raw_gains=tuple(a.raw_gains),
+                           raw_calibration=calibration_from_options(a.raw_cal, a.raw_dpc, a.cfa), raw_meta=a.raw_meta)
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

@@ -86,6 +86,13 @@ def build_parser():
                          "(--cfa, --raw-bits, --black-level, --demosaic) and resampled to --img-size in one HIP launch")
     ap.add_argument("--raw-gains", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("R", "G", "B"),
                     help="raw: per-channel multipliers on the demosaiced values (white balance)")
+    ap.add_argument("--raw-cal", default=None, metavar="FILE",
+                    help="raw: sensor calibration (.npz of python -m adaptiveisp_amd.rawcal): per-position black levels, "
+                         "white level, lens shading, defect threshold, applied in one HIP launch before the demosaic")
+    ap.add_argument("--raw-dpc", type=int, default=None, metavar="N",
+                    help="raw: defect-pixel threshold in sensor counts (overrides the calibration's; alone: defects only)")
+    ap.add_argument("--raw-meta", action="store_true",
+                    help="raw: read <stem>.json beside each plane: black_level, white_level, gains (as-shot R G B)")
     ap.add_argument("--add-noise", action="store_true", help="coco: shot + read noise")
     ap.add_argument("--bri-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="coco: random brightness ratio in [LO, HI)")
@@ -158,6 +165,10 @@ def parse_args(argv=None):
         ap.error(f"--save-param needs --batch-size 1 (got {a.batch_size})")
     if a.data_name == "raw" and a.sensor == "bayer":
         ap.error("--data-name raw with --sensor bayer: the planes already are a sensor's")
+    if a.data_name != "raw" and (a.raw_cal is not None or a.raw_dpc is not None or a.raw_meta):
+        ap.error("--raw-cal / --raw-dpc / --raw-meta need --data-name raw")
+    if a.raw_dpc is not None and a.raw_dpc < 0:
+        ap.error(f"--raw-dpc must be >= 0 (got {a.raw_dpc})")
     if a.data_name in ("lod", "raw") and (a.add_noise or a.bri_range is not None):
         print(f"note: --data-name {a.data_name} evaluates the images as they are: --add-noise / --bri-range ignored")
     if a.data_name in ("lod", "raw"):
@@ -209,6 +220,7 @@ def main(argv=None):
     from ..agent import Agent
     from ..config import cfg
     from ..data import ImageFolderSource
+    from ..rawcal import calibration_from_options
     from ..yolo import YoloEngine, yolov3
     from ..yolo.checkpoint import load_detector_checkpoint, load_isp_checkpoint
     from . import writers
@@ -244,7 +256,10 @@ def main(argv=None):
                             brightness_range=a.bri_range, noise_level=a.noise_level, use_linear=a.use_linear,
                             seed=a.seed, workers=a.workers, resize=a.resize, sensor=a.sensor, cfa=a.cfa,
                             raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic,
-                            raw_gains=tuple(a.raw_gains))
+                            raw_gains=tuple(a.raw_gains), raw_calibration=calibration_from_options(a.raw_cal, a.raw_dpc, a.cfa),
+                            raw_meta=a.raw_meta)
+    if src.raw_calibration is not None or src.raw_meta:
+        print(f"data: {src.describe()}")
     n_files = len(src)
     engines = {}
     for b in {min(a.batch_size, n_files), n_files % a.batch_size or a.batch_size}:

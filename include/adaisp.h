@@ -313,6 +313,48 @@ int adaisp_raw_load(const uint8_t* src, size_t src_bytes, const adaisp_raw_desc*
                     float white_level, void* stream);
 
 /*
+ * Raw-capture correction: what a real sensor needs before the demosaic, in one launch over a batch: defect pixels, lens
+ * shading, per-position black levels and scale. Reads the packed uint16 planes in src, writes corrected uint16 planes of the
+ * same sizes into dst; adaisp_raw_load / adaisp_demosaic_rects_ex then run on dst with one black level (black_out) and one
+ * white level. Everything is keyed by the POSITION k = 2 * (y & 1) + (x & 1) in the 2 x 2 tile (the order of the letters in
+ * the colour filter's name, the order in which cameras report black levels and DNG lays out gain maps): the function takes
+ * no pattern. desc: a DEVICE array of B records. Per sample (y, x) of image b, in this order, every operation one fp32
+ * operation (no FMA); the order and the roundings are part of the interface:
+ *   defect   v = the sample; n0..n7 = the samples of the same position at (y +- 2 or y, x +- 2 or x), centre excluded, all read
+ *            from src (never corrected values), mirrored without edge repeat at the plane's edges (period 2n - 2: the mirror
+ *            keeps the position); hi = max n, lo = min n, as integers.
+ *            dpc >= 0 and v > hi + dpc: v = hi; else dpc >= 0 and v + dpc < lo: v = lo.
+ *   shading  g = 1.0f when grid < 0; else fy = (float)y * step_y, iy = min((int)fy, grid_h - 2), ty = fy - (float)iy, the
+ *            same in x, and with T = gains + grid + k * grid_h * grid_w:
+ *                a = T[iy][ix] + tx * (T[iy][ix + 1] - T[iy][ix]),  b the same on row iy + 1,  g = a + ty * (b - a)
+ *   levels   u = ((float)v - black[k]) * g, then * scale[k], then + black_out
+ *   store    uint16 of rintf(u) (ties to even) clamped to [0, 65535]; NaN gives 0
+ * With dpc < 0, grid < 0, black[k] = black_out and scale[k] = 1 the output is a copy of the input.
+ * An image is skipped, and no byte of dst written for it, when an offset is odd, negative or out of range, its plane does not
+ * lie inside src_bytes / dst_bytes, a side is under 2, grid >= 0 with a grid side under 2 or a table that does not lie inside
+ * gain_words, or a scale is not finite.
+ * ADAISP_EINVAL: null src / dst / desc, null gains with gain_words > 0, an odd src or dst, B < 0; ADAISP_EALIAS: the byte
+ * ranges [src, src + src_bytes) and [dst, dst + dst_bytes) overlap (the defect rule reads neighbours: no in-place);
+ * ADAISP_ESHAPE: B > 65535; B == 0 is ok and launches nothing; all checked before anything touches a device.
+ * No allocation, no host synchronisation: capturable in a hipGraph.
+ */
+typedef struct adaisp_rawfix_desc {
+    int64_t src_offset;        /* byte offset of the plane's first sample in src (even)                          */
+    int64_t dst_offset;        /* byte offset of the corrected plane in dst (even)                               */
+    int32_t src_h, src_w;      /* plane size; each >= 2, any parity                                              */
+    int64_t grid;              /* word offset in gains of this image's [4][grid_h][grid_w] fp32 table; -1: none  */
+    int32_t grid_h, grid_w;    /* each >= 2 when grid >= 0                                                       */
+    float   step_y, step_x;    /* (grid_h - 1) / (src_h - 1), (grid_w - 1) / (src_w - 1) in fp32, from the host  */
+    float   black[4];          /* black level per position k                                                     */
+    float   scale[4];          /* per position: (white_out - black_out) / (white_in - black[k]) in fp32          */
+    float   black_out;         /* pedestal of the corrected plane                                                */
+    int32_t dpc;               /* defect threshold in input counts; < 0: no defect correction                    */
+    int32_t reserved[2];
+} adaisp_rawfix_desc;
+int adaisp_raw_correct(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t dst_bytes,
+                       const adaisp_rawfix_desc* desc, const float* gains, size_t gain_words, int B, void* stream);
+
+/*
  * Image export: planar fp32 RGB img [B,3,H,W] -> interleaved uint8 BGR out [B,H,W,3] (cv2.imwrite's channel order), in one
  * launch, with the arithmetic of the reference's `save_img` (util.py:21-40) and OpenCV's float -> 8U conversion:
  * NaN -> 0, clip to [0, 1], * 255.0f in fp32, round half to even. Any pointer alignment (16-byte loads where the
