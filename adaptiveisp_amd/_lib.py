@@ -293,29 +293,73 @@ def pool64_backward(grad_pooled, H, W):
 
 CFA = {"RGGB": 0, "GRBG": 1, "GBRG": 2, "BGGR": 3}
 DEMOSAIC = {"bilinear": 0, "mhc": 1}    # ADAISP_DEMOSAIC_*: 3 x 3 bilinear; 5 x 5 gradient-corrected (Malvar-He-Cutler)
+U16 = (torch.uint16, torch.int16)       # the same 16 bits: torch's uint16 is young, int16 views carry planes as well
 
 
+# ---- the front-end wrappers' argument checks (AdaispError naming the wrapper `what` and the argument, before any device work)
 def _method(what, method):
     if not isinstance(method, str) or method not in DEMOSAIC:
         raise AdaispError(f"{what}: method must be one of {sorted(DEMOSAIC)}, got {method!r}")
     return DEMOSAIC[method]
 
 
+def _pattern(pattern):
+    return CFA[pattern.upper()] if isinstance(pattern, str) else int(pattern)
+
+
+def _dtype_name(dtype):
+    return str(dtype[0] if isinstance(dtype, tuple) else dtype).replace("torch.", "")
+
+
+def _on_device(what, t, name, dtype=None):
+    """`t` is a contiguous tensor on a HIP device, of `dtype` (one, or a tuple of equivalents) when given."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise AdaispError(f"{what}: {name} must be a HIP device tensor (there is no CPU path)")
+    if not t.is_contiguous():
+        raise AdaispError(f"{what}: {name} must be contiguous")
+    if dtype is not None and t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
+        raise AdaispError(f"{what}: {name} must be a {_dtype_name(dtype)} tensor, got {t.dtype}")
+    return t
+
+
+def _records(what, desc, dtype):
+    """The number of `dtype` records (a numpy record dtype) in the device byte tensor `desc`."""
+    _on_device(what, desc, "desc", torch.uint8)
+    if desc.numel() % dtype.itemsize:
+        raise AdaispError(f"{what}: desc holds {desc.numel()} bytes, not a whole number of {dtype.itemsize}-byte records")
+    return desc.numel() // dtype.itemsize
+
+
+def _tab_words(what, tabs):
+    """The number of int32 words in the device tensor `tabs`: an int32 tensor or 4-byte aligned bytes."""
+    _on_device(what, tabs, "tabs")
+    if tabs.dtype not in (torch.uint8, torch.int32) or tabs.data_ptr() % 4 or (tabs.numel() * tabs.element_size()) % 4:
+        raise AdaispError(f"{what}: tabs must be int32 words (an int32 tensor or 4-byte aligned bytes)")
+    return tabs.numel() * tabs.element_size() // 4
+
+
+def _out(what, out, shape, dtype, device, alloc=None):
+    """`out` if it is a contiguous `dtype` tensor of `shape` on `device`; a new one (of shape `alloc`, else `shape`) for None."""
+    if out is None:
+        return torch.empty(alloc or shape, dtype=dtype[0] if isinstance(dtype, tuple) else dtype, device=device)
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device
+            or out.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,))):
+        raise AdaispError(f"{what}: out must be a contiguous {_dtype_name(dtype)} [{','.join(map(str, shape))}] tensor on the "
+                          f"HIP device {device}")
+    return out
+
+
 def demosaic(raw, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None, method="bilinear"):
     """Bayer front-end: raw uint16 [B,H,W] on the device -> planar fp32 [B,3,H,W] in [0,1] (include/adaisp.h); `method`
     "bilinear" or "mhc" (adaisp_demosaic_ex; "mhc" is not clamped and can leave [0,1] at edges)."""
     L, meth = load(), _method("demosaic", method)
-    if raw.device.type != "cuda":
-        raise AdaispError("demosaic: raw must live on a HIP device (there is no CPU path)")
-    if raw.dtype not in (torch.uint16, torch.int16) or raw.dim() != 3:
+    raw = _on_device("demosaic", raw.contiguous() if isinstance(raw, torch.Tensor) else raw, "raw")
+    if raw.dtype not in U16 or raw.dim() != 3:
         raise AdaispError(f"demosaic: raw must be uint16 [B,H,W], got {raw.dtype} {tuple(raw.shape)}")
-    raw = raw.contiguous()
     B, H, W = raw.shape
-    if out is None:
-        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=raw.device)
-    pat = CFA[pattern.upper()] if isinstance(pattern, str) else int(pattern)
+    out = _out("demosaic", out, (B, 3, H, W), torch.float32, raw.device)
     with torch.cuda.device(raw.device):
-        rc = L.adaisp_demosaic_ex(raw.data_ptr(), out.data_ptr(), B, H, W, pat, meth, float(black_level),
+        rc = L.adaisp_demosaic_ex(raw.data_ptr(), out.data_ptr(), B, H, W, _pattern(pattern), meth, float(black_level),
                                   float(white_level), _stream())
     _check(rc, "adaisp_demosaic_ex")
     _wrote(out)
@@ -333,18 +377,9 @@ def unprocess(src, desc, S, seed=0, flags=0, out=None):
     planar fp32 [B,3,S,S], letterboxed by `desc` (B records of UNPROCESS_DESC as a device byte tensor). flags: 0 (u8 / 255),
     UNP_UNPROCESS, UNP_UNPROCESS | UNP_NOISE. Raises on bad arguments before any device work."""
     L = load()
-    for t, name in ((src, "src"), (desc, "desc")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AdaispError(f"unprocess: {name} must be a HIP device tensor (there is no CPU path)")
-        if t.dtype != torch.uint8 or not t.is_contiguous():
-            raise AdaispError(f"unprocess: {name} must be a contiguous uint8 tensor, got {t.dtype}")
-    if desc.numel() % UNPROCESS_DESC.itemsize:
-        raise AdaispError(f"unprocess: desc holds {desc.numel()} bytes, not a whole number of {UNPROCESS_DESC.itemsize}-byte records")
-    B, S = desc.numel() // UNPROCESS_DESC.itemsize, int(S)
-    if out is None:
-        out = torch.empty((max(B, 1), 3, max(S, 1), max(S, 1)), dtype=torch.float32, device=src.device)
-    elif tuple(out.shape) != (B, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
-        raise AdaispError(f"unprocess: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {src.device}")
+    _on_device("unprocess", src, "src", torch.uint8)
+    B, S = _records("unprocess", desc, UNPROCESS_DESC), int(S)
+    out = _out("unprocess", out, (B, 3, S, S), torch.float32, src.device, alloc=(max(B, 1), 3, max(S, 1), max(S, 1)))
     with torch.cuda.device(src.device):
         rc = L.adaisp_unprocess(src.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, int(seed) & (2 ** 64 - 1),
                                 int(flags), _stream())
@@ -353,33 +388,14 @@ def unprocess(src, desc, S, seed=0, flags=0, out=None):
     return out
 
 
-def _bytes_on_device(what, tensors):
-    for t, name in tensors:
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AdaispError(f"{what}: {name} must be a HIP device tensor (there is no CPU path)")
-        if t.dtype != torch.uint8 or not t.is_contiguous():
-            raise AdaispError(f"{what}: {name} must be a contiguous uint8 tensor, got {t.dtype}")
-    desc = tensors[-1][0]
-    if desc.numel() % UNPROCESS_DESC.itemsize:
-        raise AdaispError(f"{what}: desc holds {desc.numel()} bytes, not a whole number of {UNPROCESS_DESC.itemsize}-byte records")
-    return desc.numel() // UNPROCESS_DESC.itemsize
-
-
-def _pattern(pattern):
-    return CFA[pattern.upper()] if isinstance(pattern, str) else int(pattern)
-
-
 def unprocess_bayer(src, desc, S, seed=0, flags=0, pattern="RGGB", black_level=0.0, white_level=65535.0, out=None):
     """adaisp_unprocess_bayer: `unprocess` seen through a colour filter array and quantised -> uint16 [B,S,S] on the
     device. src / desc / S / seed / flags as `unprocess`; a sample is the channel the CFA keeps at that pixel of the image
     (phase from the image's origin), clamp(rint(v * (white - black)) + black, 0, 65535), and `black` outside the image."""
     L = load()
-    B, S = _bytes_on_device("unprocess_bayer", ((src, "src"), (desc, "desc"))), int(S)
-    if out is None:
-        out = torch.empty((max(B, 1), max(S, 1), max(S, 1)), dtype=torch.uint16, device=src.device)
-    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, S, S) or out.dtype not in (torch.uint16, torch.int16)
-          or not out.is_contiguous() or out.device != src.device):
-        raise AdaispError(f"unprocess_bayer: out must be a contiguous uint16 [{B},{S},{S}] tensor on {src.device}")
+    _on_device("unprocess_bayer", src, "src", torch.uint8)
+    B, S = _records("unprocess_bayer", desc, UNPROCESS_DESC), int(S)
+    out = _out("unprocess_bayer", out, (B, S, S), U16, src.device, alloc=(max(B, 1), max(S, 1), max(S, 1)))
     with torch.cuda.device(src.device):
         rc = L.adaisp_unprocess_bayer(src.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, int(seed) & (2 ** 64 - 1),
                                       int(flags), _pattern(pattern), float(black_level), float(white_level), _stream())
@@ -393,19 +409,14 @@ def demosaic_rects(raw, desc, pattern="RGGB", black_level=0.0, white_level=65535
     fp32 [B,3,S,S]: `demosaic` (same `method`) inside every image's own rectangle (phase and mirror at the rectangle),
     exactly 0 outside."""
     L, meth = load(), _method("demosaic_rects", method)
-    if not isinstance(raw, torch.Tensor) or raw.device.type != "cuda":
-        raise AdaispError("demosaic_rects: raw must be a HIP device tensor (there is no CPU path)")
-    B = _bytes_on_device("demosaic_rects", ((desc, "desc"),))
-    if raw.dtype not in (torch.uint16, torch.int16) or raw.dim() != 3 or raw.shape[1] != raw.shape[2] or not raw.is_contiguous():
+    _on_device("demosaic_rects", raw, "raw")
+    B = _records("demosaic_rects", desc, UNPROCESS_DESC)
+    if raw.dtype not in U16 or raw.dim() != 3 or raw.shape[1] != raw.shape[2]:
         raise AdaispError(f"demosaic_rects: raw must be a contiguous uint16 [B,S,S] tensor, got {raw.dtype} {tuple(raw.shape)}")
     if raw.shape[0] != B or raw.device != desc.device:
         raise AdaispError(f"demosaic_rects: {raw.shape[0]} planes on {raw.device} but {B} descriptors on {desc.device}")
     S = int(raw.shape[1])
-    if out is None:
-        out = torch.empty((B, 3, S, S), dtype=torch.float32, device=raw.device)
-    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, 3, S, S) or out.dtype != torch.float32
-          or not out.is_contiguous() or out.device != raw.device):
-        raise AdaispError(f"demosaic_rects: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {raw.device}")
+    out = _out("demosaic_rects", out, (B, 3, S, S), torch.float32, raw.device)
     with torch.cuda.device(raw.device):
         rc = L.adaisp_demosaic_rects_ex(raw.data_ptr(), desc.data_ptr(), out.data_ptr(), B, S, _pattern(pattern), meth,
                                         float(black_level), float(white_level), _stream())
@@ -457,23 +468,13 @@ def resize_u8(src, dst, desc, tabs, records):
     int32 tensor or a 4-byte aligned byte tensor, or None when no image needs taps. `records` (host) sizes the launch and
     is checked against the buffers: raises on host tensors or malformed records before any device work. Capturable."""
     L = load()
-    for t, name in ((src, "src"), (dst, "dst"), (desc, "desc")) + (() if tabs is None else ((tabs, "tabs"),)):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AdaispError(f"resize_u8: {name} must be a HIP device tensor (there is no CPU path)")
-        if not t.is_contiguous():
-            raise AdaispError(f"resize_u8: {name} must be contiguous")
     for t, name in ((src, "src"), (dst, "dst"), (desc, "desc")):
-        if t.dtype != torch.uint8:
-            raise AdaispError(f"resize_u8: {name} must be a uint8 tensor, got {t.dtype}")
+        _on_device("resize_u8", t, name, torch.uint8)
+    tab_words = 0 if tabs is None else _tab_words("resize_u8", tabs)
     if not isinstance(records, np.ndarray) or records.dtype != RESIZE_DESC or records.ndim != 1 or len(records) < 1:
         raise AdaispError("resize_u8: records must be a non-empty 1-D numpy array of RESIZE_DESC")
     if desc.numel() != records.nbytes:
         raise AdaispError(f"resize_u8: desc holds {desc.numel()} bytes, records {records.nbytes}")
-    tab_words = 0
-    if tabs is not None:
-        if tabs.dtype not in (torch.uint8, torch.int32) or tabs.data_ptr() % 4 or (tabs.numel() * tabs.element_size()) % 4:
-            raise AdaispError("resize_u8: tabs must be int32 words (an int32 tensor or 4-byte aligned bytes)")
-        tab_words = tabs.numel() * tabs.element_size() // 4
     _check_resize_records(records, src.numel(), dst.numel(), tab_words)
     B = len(records)
     with torch.cuda.device(src.device):
@@ -499,32 +500,17 @@ def raw_load(src, desc, tabs, S, pattern="RGGB", method="bilinear", black_level=
     or 4-byte aligned bytes) and placed as `desc` (B records of RAW_DESC as a device byte tensor) says, 0 around it. Raises
     on bad arguments before any device work."""
     L, meth = load(), _method("raw_load", method)
-    for t, name in ((src, "src"), (desc, "desc"), (tabs, "tabs")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AdaispError(f"raw_load: {name} must be a HIP device tensor (there is no CPU path)")
-        if not t.is_contiguous():
-            raise AdaispError(f"raw_load: {name} must be contiguous")
-    for t, name in ((src, "src"), (desc, "desc")):
-        if t.dtype != torch.uint8:
-            raise AdaispError(f"raw_load: {name} must be a uint8 tensor, got {t.dtype}")
+    _on_device("raw_load", src, "src", torch.uint8)
+    B, S = _records("raw_load", desc, RAW_DESC), int(S)
+    tab_words = _tab_words("raw_load", tabs)
     if src.data_ptr() % 2:
         raise AdaispError("raw_load: src must be 2-byte aligned (uint16 samples)")
-    if desc.numel() % RAW_DESC.itemsize:
-        raise AdaispError(f"raw_load: desc holds {desc.numel()} bytes, not a whole number of {RAW_DESC.itemsize}-byte records")
-    if tabs.dtype not in (torch.uint8, torch.int32) or tabs.data_ptr() % 4 or (tabs.numel() * tabs.element_size()) % 4:
-        raise AdaispError("raw_load: tabs must be int32 words (an int32 tensor or 4-byte aligned bytes)")
     if desc.device != src.device or tabs.device != src.device:
         raise AdaispError(f"raw_load: src on {src.device}, desc on {desc.device}, tabs on {tabs.device}")
-    B, S = desc.numel() // RAW_DESC.itemsize, int(S)
-    if out is None:
-        out = torch.empty((B, 3, max(S, 1), max(S, 1)), dtype=torch.float32, device=src.device)
-    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, 3, S, S) or out.dtype != torch.float32
-          or not out.is_contiguous() or out.device != src.device):
-        raise AdaispError(f"raw_load: out must be a contiguous float32 [{B},3,{S},{S}] tensor on {src.device}")
+    out = _out("raw_load", out, (B, 3, S, S), torch.float32, src.device, alloc=(B, 3, max(S, 1), max(S, 1)))
     with torch.cuda.device(src.device):
-        rc = L.adaisp_raw_load(src.data_ptr(), src.numel(), desc.data_ptr(), tabs.data_ptr(),
-                               tabs.numel() * tabs.element_size() // 4, out.data_ptr(), B, S, _pattern(pattern), meth,
-                               float(black_level), float(white_level), _stream())
+        rc = L.adaisp_raw_load(src.data_ptr(), src.numel(), desc.data_ptr(), tabs.data_ptr(), tab_words, out.data_ptr(), B, S,
+                               _pattern(pattern), meth, float(black_level), float(white_level), _stream())
     _check(rc, "adaisp_raw_load")
     _wrote(out)
     return out
@@ -544,22 +530,13 @@ def raw_correct(src, desc, gains=None, out=None):
     defect pixels, shading gain from the tables in `gains` (a device float32 tensor, or None when no record has one),
     per-position black levels and scale. `out` must not overlap `src`. Raises on bad arguments before any device work."""
     L = load()
-    named = ((src, "src"), (desc, "desc")) + (() if out is None else ((out, "out"),)) + (() if gains is None else ((gains, "gains"),))
-    for t, name in named:
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AdaispError(f"raw_correct: {name} must be a HIP device tensor (there is no CPU path)")
-        if not t.is_contiguous():
-            raise AdaispError(f"raw_correct: {name} must be contiguous")
-        if t.device != src.device:
+    given = [(src, "src", torch.uint8), (desc, "desc", torch.uint8)]
+    given += [] if gains is None else [(gains, "gains", torch.float32)]
+    given += [] if out is None else [(out, "out", torch.uint8)]
+    for t, name, dtype in given:
+        if _on_device("raw_correct", t, name, dtype).device != src.device:
             raise AdaispError(f"raw_correct: src on {src.device}, {name} on {t.device}")
-        if name != "gains" and t.dtype != torch.uint8:
-            raise AdaispError(f"raw_correct: {name} must be a uint8 tensor, got {t.dtype}")
-    if gains is not None and gains.dtype != torch.float32:
-        raise AdaispError(f"raw_correct: gains must be a float32 tensor, got {gains.dtype}")
-    if desc.numel() % RAWFIX_DESC.itemsize:
-        raise AdaispError(f"raw_correct: desc holds {desc.numel()} bytes, not a whole number of {RAWFIX_DESC.itemsize}-byte "
-                          "records")
-    B = desc.numel() // RAWFIX_DESC.itemsize
+    B = _records("raw_correct", desc, RAWFIX_DESC)
     if B > 65535:
         raise AdaispError(f"raw_correct: {B} records, at most 65535 per launch")
     if out is None:
@@ -585,11 +562,7 @@ def export_u8(img, out=None):
     L = load()
     img = _dev_f32(img.detach(), "img")
     B, H, W = _img_shape(img)
-    if out is None:
-        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=img.device)
-    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, H, W, 3) or out.dtype != torch.uint8
-          or not out.is_contiguous() or out.device != img.device):
-        raise AdaispError(f"export_u8: out must be a contiguous uint8 [{B},{H},{W},3] tensor on {img.device}")
+    out = _out("export_u8", out, (B, H, W, 3), torch.uint8, img.device)
     with torch.cuda.device(img.device):
         rc = L.adaisp_export_u8(img.data_ptr(), out.data_ptr(), B, H, W, _stream())
     _check(rc, "adaisp_export_u8")

@@ -81,35 +81,28 @@ int adaisp_pool64_backward(const float* grad_pooled, float* grad_img, int B, int
 
 int adaisp_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black_level,
                     float white_level, void* stream) {
-    if (int rc = check_demosaic(raw, out, B, H, W, pattern, black_level, white_level)) return rc;
-    return launch_demosaic(raw, out, B, H, W, pattern, black_level, white_level, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+    return adaisp_demosaic_ex(raw, out, B, H, W, pattern, ADAISP_DEMOSAIC_BILINEAR, black_level, white_level, stream);
 }
 
 int adaisp_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S, int pattern,
                           float black_level, float white_level, void* stream) {
-    if (int rc = check_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level)) return rc;
-    return launch_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level,
-                                 static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+    return adaisp_demosaic_rects_ex(raw, desc, out, B, S, pattern, ADAISP_DEMOSAIC_BILINEAR, black_level, white_level, stream);
 }
 
 int adaisp_demosaic_ex(const uint16_t* raw, float* out, int B, int H, int W, int pattern, int method, float black_level,
                        float white_level, void* stream) {
-    if (method == ADAISP_DEMOSAIC_BILINEAR) return adaisp_demosaic(raw, out, B, H, W, pattern, black_level, white_level, stream);
-    if (method != ADAISP_DEMOSAIC_MHC) return ADAISP_EINVAL;
+    if (method != ADAISP_DEMOSAIC_BILINEAR && method != ADAISP_DEMOSAIC_MHC) return ADAISP_EINVAL;
     if (int rc = check_demosaic(raw, out, B, H, W, pattern, black_level, white_level)) return rc;
-    return launch_demosaic_mhc(raw, out, B, H, W, pattern, black_level, white_level, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+    return launch_demosaic(method, raw, nullptr, out, B, H, W, pattern, black_level, white_level,
+                           static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }
 
 int adaisp_demosaic_rects_ex(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S, int pattern,
                              int method, float black_level, float white_level, void* stream) {
-    if (method == ADAISP_DEMOSAIC_BILINEAR)
-        return adaisp_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level, stream);
-    if (method != ADAISP_DEMOSAIC_MHC) return ADAISP_EINVAL;
+    if (method != ADAISP_DEMOSAIC_BILINEAR && method != ADAISP_DEMOSAIC_MHC) return ADAISP_EINVAL;
     if (int rc = check_demosaic_rects(raw, desc, out, B, S, pattern, black_level, white_level)) return rc;
-    return launch_demosaic_mhc_rects(raw, desc, out, B, S, pattern, black_level, white_level,
-                                     static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+    return launch_demosaic(method, raw, desc, out, B, S, S, pattern, black_level, white_level,
+                           static_cast<hipStream_t>(stream)) == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }
 
 int adaisp_process(int op, const float* img, float* out, const float* params, int param_stride, int B, int H, int W,

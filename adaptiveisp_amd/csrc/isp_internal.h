@@ -79,14 +79,9 @@ hipError_t launch_nlm_general(const float* img, float* out, const float* h, int 
                               int search, int patch, hipStream_t s);
 hipError_t launch_pool64(const float* img, float* pooled, int B, int H, int W, hipStream_t s);
 hipError_t launch_pool64_bwd(const float* grad_pooled, float* grad_img, int B, int H, int W, hipStream_t s);
-hipError_t launch_demosaic(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black, float white,
-                           hipStream_t s);
-hipError_t launch_demosaic_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
-                                 int pattern, float black, float white, hipStream_t s);
-hipError_t launch_demosaic_mhc(const uint16_t* raw, float* out, int B, int H, int W, int pattern, float black, float white,
-                               hipStream_t s);
-hipError_t launch_demosaic_mhc_rects(const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int S,
-                                     int pattern, float black, float white, hipStream_t s);
+// method: ADAISP_DEMOSAIC_*; desc null: the image is the [FH,FW] frame; else image b in its rectangle desc[b] of the frame
+hipError_t launch_demosaic(int method, const uint16_t* raw, const adaisp_unprocess_desc* desc, float* out, int B, int FH,
+                           int FW, int pattern, float black, float white, hipStream_t s);
 hipError_t launch_backward_params(const float* img, const float* grad_out, const int32_t* ids,
                                   const float* params, int pstride, float* grad_params,
                                   int B, int H, int W, unsigned flags, hipStream_t s);

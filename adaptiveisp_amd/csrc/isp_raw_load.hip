@@ -36,26 +36,7 @@ constexpr int RL_WIN = 5;                       // row slots
 
 __device__ __forceinline__ int swz(int l) { return l + (l >> 5); }
 
-template <int METHOD>
-__device__ __forceinline__ float raw_sample(unsigned v, float black, float inv_range) {
-    const float t = (float)v - black;
-    return METHOD == ADAISP_DEMOSAIC_MHC ? t : t * inv_range;
-}
-
-// the three colours of a site from its neighbourhood at(dy, dx), samples as raw_sample<METHOD> gives them
-template <int METHOD, class At>
-__device__ __forceinline__ void raw_site(At at, int py, int px, float inv_range, float& r, float& g, float& b) {
-    const float c = at(0, 0);
-    if (METHOD == ADAISP_DEMOSAIC_MHC) {
-        const float a1h = at(0, -1) + at(0, 1), a1v = at(-1, 0) + at(1, 0);
-        const float a2h = at(0, -2) + at(0, 2), a2v = at(-2, 0) + at(2, 0);
-        const float d = (at(-1, -1) + at(-1, 1)) + (at(1, -1) + at(1, 1));
-        mhc_site_sums(c, a1h, a1v, a2h, a2v, d, py, px, inv_range, r, g, b);
-    } else {
-        bilinear_site(c, at(-1, 0), at(1, 0), at(0, -1), at(0, 1), at(-1, -1), at(-1, 1), at(1, -1), at(1, 1), py, px, r, g,
-                      b);
-    }
-}
+// raw_sample<METHOD>() and raw_site<METHOD>(): isp_demosaic_math.h
 
 template <int METHOD>
 __global__ __launch_bounds__(RL_THREADS) void k_raw_load(const uint8_t* __restrict__ src, int64_t src_bytes,

@@ -24,6 +24,7 @@ import os
 import random
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -87,6 +88,33 @@ def kernel_params(meta, prescale=PRESCALE):
     p[9:12] = np.stack((1.0 / meta["red_gain"], 1.0, 1.0 / meta["blue_gain"])) / meta["rgb_gain"]
     p[12], p[13], p[14], p[15] = prescale, meta["gain"], meta["shot"], meta["read"]
     return p
+
+
+class Item(NamedTuple):
+    """One decoded file, as the worker threads hand it to the batch builders. What `pixels`, `size` and `unpad` hold:
+      resize="host"     pixels: load_letterboxed's uint8 HWC BGR image, already at its final size; size, unpad: None
+      resize="device"   pixels: the decoded uint8 HWC BGR image as it is; size: (h, w) after load_image's resample;
+                        unpad: (h2, w2) after letterbox's (letterboxed_geometry): what the device makes of it
+      data_name="raw"   pixels: the memory-mapped uint16 plane at the sensor's size; size: as for resize="device", unused
+                        (there is no second pass); unpad: the (h2, w2) the plane is resampled to
+    (top, left) place the final image in the S x S frame; label is [k,6] float32 with column 0 zero."""
+    pixels: np.ndarray
+    top: int
+    left: int
+    label: np.ndarray
+    path: str
+    shapes: tuple
+    size: tuple = None
+    unpad: tuple = None
+
+
+def _sections(start, *nbytes):
+    """Consecutive 16-byte aligned sections of `nbytes` bytes each from `start` on: their offsets, then the aligned end."""
+    offsets = []
+    for n in nbytes:
+        offsets.append(start)
+        start = (start + n + 15) // 16 * 16
+    return (*offsets, start)
 
 
 class ImageFolderSource:
@@ -269,29 +297,18 @@ class ImageFolderSource:
         return i
 
     def _decode(self, i):
-        """(im, top, left, label, path, shapes, sizes): with resize="device" `im` is the decoded image as it is and `sizes`
-        ((h, w) after load_image, (h2, w2) after letterbox's resize) says what the device makes of it; otherwise `im` is
-        load_letterboxed's and `sizes` None."""
+        """File i as an Item (which says what its fields hold in each mode)."""
         path = self.files[i]
-        if self.data_name == "raw":
-            plane = open_raw_plane(path)
-            size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(plane.shape[0], plane.shape[1],
-                                                                                       self.img_size)
-            lb = letterboxed_labels(path, size, frame, ratio, pad)
-            label = np.zeros((len(lb), 6), np.float32)
-            label[:, 1:] = lb
-            return plane, top, left, label, path, shapes, unpad
-        if self.resize == "device":
-            im = imread_bgr(path)
-            size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(im.shape[0], im.shape[1],
-                                                                                       self.img_size)
-            lb, sizes = letterboxed_labels(path, size, frame, ratio, pad), (size, unpad)
-        else:
+        if self.data_name != "raw" and self.resize != "device":
             im, (top, left), _, lb, shapes = load_letterboxed(path, self.img_size)
-            sizes = None
+            size = unpad = None
+        else:
+            im = open_raw_plane(path) if self.data_name == "raw" else imread_bgr(path)
+            size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(im.shape[0], im.shape[1], self.img_size)
+            lb = letterboxed_labels(path, size, frame, ratio, pad)
         label = np.zeros((len(lb), 6), np.float32)
         label[:, 1:] = lb
-        return im, top, left, label, path, shapes, sizes
+        return Item(im, top, left, label, path, shapes, size, unpad)
 
     def _take(self, n):
         """The next n decoded items; with workers, keeps up to 2 * n more decoding behind them."""
@@ -306,7 +323,7 @@ class ImageFolderSource:
     def get_next_batch(self, n):
         n = int(n)
         items = self._take(n)
-        labels, paths, shapes = [it[3] for it in items], [it[4] for it in items], [it[5] for it in items]
+        labels, paths, shapes = [it.label for it in items], [it.path for it in items], [it.shapes for it in items]
         if self.device.type != "cuda":
             return list(self._cpu_lod(items)), labels, paths, shapes
         return list(self._device_batch(items)), labels, paths, shapes
@@ -314,9 +331,10 @@ class ImageFolderSource:
     def _cpu_lod(self, items):
         S = self.img_size
         out = torch.zeros((len(items), 3, S, S))
-        for b, (im, top, left, *_rest) in enumerate(items):
-            chw = np.ascontiguousarray(im.transpose(2, 0, 1)[::-1])
-            out[b, :, top:top + im.shape[0], left:left + im.shape[1]] = torch.from_numpy(chw).float() / 255.0
+        for b, it in enumerate(items):
+            h, w = it.pixels.shape[:2]
+            chw = np.ascontiguousarray(it.pixels.transpose(2, 0, 1)[::-1])
+            out[b, :, it.top:it.top + h, it.left:it.left + w] = torch.from_numpy(chw).float() / 255.0
         return out.to(self.device)
 
     def _resize_plan(self, items, head):
@@ -329,9 +347,9 @@ class ImageFolderSource:
         S = self.img_size
         p1 = TapPlan()
         sizes, pix = [], 0
-        for im, *_rest, (size, unpad) in items:
-            sizes.append((im.shape[:2], pix, size, unpad))
-            pix += im.size
+        for it in items:
+            sizes.append((it.pixels.shape[:2], pix, it.size, it.unpad))
+            pix += it.pixels.size
         off1, at1 = 0, {}
         for b, (full, src_off, size, _unpad) in enumerate(sizes):
             if tuple(size) != tuple(full):
@@ -351,12 +369,28 @@ class ImageFolderSource:
                 final.append((full[0], full[1], src_off))
         rec1, rec2 = p1.descriptors(), p2.descriptors()
         tab = np.concatenate([p1.table(), p2.table()])
-        r1 = head
-        r2 = r1 + (rec1.nbytes + 15) // 16 * 16
-        tb = r2 + (rec2.nbytes + 15) // 16 * 16
-        base = tb + (tab.nbytes + 15) // 16 * 16
+        r1, r2, tb, base = _sections(head, rec1.nbytes, rec2.nbytes, tab.nbytes)
         lay = dict(rec1=rec1, rec2=rec2, tab=tab, r1=r1, r2=r2, tb=tb, base=base, s1=off1, s2=off2)
         return lay, final
+
+    def _stage(self, total, fill, scratch=0, room=0):
+        """What every batch does with its bytes: the next pinned slot, once the event of its previous copy has completed;
+        host and device buffers grown to `total` bytes (the host at least to `room`, the device by `scratch` more, which
+        only kernels write); `fill(host)` writes the first `total` bytes of the slot (a numpy view); the batch's one H2D
+        copy, non-blocking on the current stream, and the slot's event behind it. Returns the device buffer."""
+        slot = self._slots[self._slot]
+        self._slot = (self._slot + 1) % len(self._slots)
+        if slot["event"] is not None:
+            slot["event"].synchronize()           # this slot's previous H2D copy has finished reading it
+        if slot["host"] is None or slot["host"].numel() < total:
+            slot["host"] = torch.empty(max(total, room), dtype=torch.uint8, pin_memory=True)
+        fill(slot["host"].numpy())
+        if self._dev is None or self._dev.numel() < total + scratch:
+            self._dev = torch.empty(max(slot["host"].numel(), total + scratch), dtype=torch.uint8, device=self.device)
+        self._dev[:total].copy_(slot["host"][:total], non_blocking=True)
+        slot["event"] = torch.cuda.Event()
+        slot["event"].record()
+        return self._dev
 
     def _raw_batch(self, items):
         """data_name="raw": one pinned buffer (descriptors, tap tables, the planes, each 16-byte aligned), one H2D copy, one
@@ -368,69 +402,56 @@ class ImageFolderSource:
         from .rawcal import fill_rawfix, level_scale, resolve
         from .resize import RawTapPlan
         S, B = self.img_size, len(items)
-        plan, at, pos = RawTapPlan(), [], 0
-        for plane, top, left, _lb, path, _shapes, unpad in items:
-            if min(plane.shape) < 2:
-                raise ValueError(f"{path}: {plane.shape[0]} x {plane.shape[1]} samples: a raw plane needs at least 2 x 2")
-            meta = self._meta.get(path) or {}
-            plan.add(plane.shape, unpad, (top, left), pos, meta.get("gains", self.raw_gains))
-            at.append(pos)
-            pos = (pos + plane.nbytes + 15) // 16 * 16
+        *at, pos = _sections(0, *(it.pixels.nbytes for it in items))          # the planes, relative to the first
+        plan = RawTapPlan()
+        for it, off in zip(items, at):
+            if min(it.pixels.shape) < 2:
+                raise ValueError(f"{it.path}: {it.pixels.shape[0]} x {it.pixels.shape[1]} samples: a raw plane needs at least "
+                                 "2 x 2")
+            meta = self._meta.get(it.path) or {}
+            plan.add(it.pixels.shape, it.unpad, (it.top, it.left), off, meta.get("gains", self.raw_gains))
         self.serial += B
         desc, tab = plan.descriptors(), plan.table()
-        dbytes = (desc.nbytes + 15) // 16 * 16
-        base = dbytes + (tab.nbytes + 15) // 16 * 16
+        _, dbytes, base = _sections(0, desc.nbytes, tab.nbytes)
         fix = shading = None
         if self._rawfix:
             cal = self.raw_calibration
             shading = None if cal is None else cal.shading
             fix = np.zeros(B, _lib.RAWFIX_DESC)
-            for k, (plane, _t, _l, _lb, path, *_rest) in enumerate(items):
-                black, white = resolve(cal, self._meta.get(path), self.black_level, self.white_level, where=path)
-                fill_rawfix(fix[k], plane.shape, at[k], at[k], black,
+            for k, it in enumerate(items):
+                black, white = resolve(cal, self._meta.get(it.path), self.black_level, self.white_level, where=it.path)
+                fill_rawfix(fix[k], it.pixels.shape, at[k], at[k], black,
                             level_scale(black, white, self.black_level, self.white_level), self.black_level,
                             None if cal is None else cal.dpc, None if shading is None else (0, *shading.shape[1:]))
-            fbase = base
-            gbase = fbase + (fix.nbytes + 15) // 16 * 16
-            base = gbase + ((0 if shading is None else shading.nbytes) + 15) // 16 * 16
+            fbase, gbase, base = _sections(base, fix.nbytes, 0 if shading is None else shading.nbytes)
         total = base + pos
-        slot = self._slots[self._slot]
-        self._slot = (self._slot + 1) % len(self._slots)
-        if slot["event"] is not None:
-            slot["event"].synchronize()           # this slot's previous H2D copy has finished reading it
-        if slot["host"] is None or slot["host"].numel() < total:
-            slot["host"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        host = slot["host"].numpy()
-        host[:desc.nbytes] = desc.view(np.uint8)
-        host[dbytes:dbytes + tab.nbytes] = tab.view(np.uint8)
-        if fix is not None:
-            host[fbase:fbase + fix.nbytes] = fix.view(np.uint8)
-            if shading is not None:
-                host[gbase:gbase + shading.nbytes] = shading.reshape(-1).view(np.uint8)
 
-        def copy(k):                              # the one host pass over the samples: mapping -> pinned slot
-            plane = items[k][0]
-            host[base + at[k]:base + at[k] + plane.nbytes].view(np.uint16).reshape(plane.shape)[...] = plane
-
-        if self._pool is not None:
-            list(self._pool.map(copy, range(B)))
-        else:
-            for k in range(B):
-                copy(k)
-        with torch.cuda.device(self.device):
-            need = total + (pos if fix is not None else 0)
-            if self._dev is None or self._dev.numel() < need:
-                self._dev = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._dev[:total].copy_(slot["host"][:total], non_blocking=True)
-            slot["event"] = torch.cuda.Event()
-            slot["event"].record()
-            planes = self._dev[base:total]
+        def fill(host):
+            host[:desc.nbytes] = desc.view(np.uint8)
+            host[dbytes:dbytes + tab.nbytes] = tab.view(np.uint8)
             if fix is not None:
-                gains = None if shading is None else self._dev[gbase:gbase + shading.nbytes].view(torch.float32)
-                planes = _lib.raw_correct(planes, self._dev[fbase:fbase + fix.nbytes], gains, out=self._dev[total:total + pos])
-            return _lib.raw_load(planes, self._dev[:desc.nbytes], self._dev[dbytes:dbytes + tab.nbytes], S,
-                                 pattern=self.cfa, method=self.demosaic, black_level=self.black_level,
-                                 white_level=self.white_level)
+                host[fbase:fbase + fix.nbytes] = fix.view(np.uint8)
+                if shading is not None:
+                    host[gbase:gbase + shading.nbytes] = shading.reshape(-1).view(np.uint8)
+
+            def copy(k):                          # the one host pass over the samples: mapping -> pinned slot
+                plane = items[k].pixels
+                host[base + at[k]:base + at[k] + plane.nbytes].view(np.uint16).reshape(plane.shape)[...] = plane
+
+            if self._pool is not None:
+                list(self._pool.map(copy, range(B)))
+            else:
+                for k in range(B):
+                    copy(k)
+
+        with torch.cuda.device(self.device):
+            dev = self._stage(total, fill, scratch=pos if fix is not None else 0)
+            planes = dev[base:total]
+            if fix is not None:
+                gains = None if shading is None else dev[gbase:gbase + shading.nbytes].view(torch.float32)
+                planes = _lib.raw_correct(planes, dev[fbase:fbase + fix.nbytes], gains, out=dev[total:total + pos])
+            return _lib.raw_load(planes, dev[:desc.nbytes], dev[dbytes:dbytes + tab.nbytes], S, pattern=self.cfa,
+                                 method=self.demosaic, black_level=self.black_level, white_level=self.white_level)
 
     def _device_batch(self, items):
         from . import _lib
@@ -438,20 +459,20 @@ class ImageFolderSource:
             return self._raw_batch(items)
         S, B = self.img_size, len(items)
         desc = np.zeros(B, _lib.UNPROCESS_DESC)
-        dbytes = (B * _lib.UNPROCESS_DESC.itemsize + 15) // 16 * 16
+        _, dbytes = _sections(0, desc.nbytes)
         lay = None
         if self.resize == "device":
             lay, final = self._resize_plan(items, dbytes)
         else:
             final, off = [], 0
-            for im, *_rest in items:
-                final.append((im.shape[0], im.shape[1], off))
-                off += im.size
-        for b, ((h, w, src_offset), (im, top, left, *_rest)) in enumerate(zip(final, items)):
+            for it in items:
+                final.append((it.pixels.shape[0], it.pixels.shape[1], off))
+                off += it.pixels.size
+        for b, ((h, w, src_offset), it) in enumerate(zip(final, items)):
             if self.sensor == "bayer" and min(h, w) < 2:
-                raise ValueError(f"{items[b][4]}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
+                raise ValueError(f"{it.path}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
             desc[b]["src_offset"], desc[b]["h"], desc[b]["w"] = src_offset, h, w
-            desc[b]["top"], desc[b]["left"], desc[b]["serial"] = top, left, self.serial
+            desc[b]["top"], desc[b]["left"], desc[b]["serial"] = it.top, it.left, self.serial
             self.serial += 1
         flags = 0
         if self.data_name == "coco":
@@ -460,32 +481,24 @@ class ImageFolderSource:
                 desc[b]["p"] = kernel_params(sample_unprocess_params(self.rs, self.add_noise, self.brightness_range,
                                                                      self.noise_level, self.use_linear))
         base = dbytes if lay is None else lay["base"]                   # where the staged pixels start
-        total = base + sum(it[0].size for it in items)
+        total = base + sum(it.pixels.size for it in items)
         need = total if lay is None else total + lay["s1"] + lay["s2"]
-        slot = self._slots[self._slot]
-        self._slot = (self._slot + 1) % len(self._slots)
-        if slot["event"] is not None:
-            slot["event"].synchronize()           # this slot's previous H2D copy has finished reading it
-        if slot["host"] is None or slot["host"].numel() < total:
-            slot["host"] = torch.empty(max(total, dbytes + B * S * S * 3), dtype=torch.uint8, pin_memory=True)
-        host = slot["host"].numpy()
-        host[:B * desc.itemsize] = desc.view(np.uint8)
-        if lay is not None:
-            for key, at in (("rec1", "r1"), ("rec2", "r2"), ("tab", "tb")):
-                host[lay[at]:lay[at] + lay[key].nbytes] = lay[key].view(np.uint8)
-        pos = base
-        for im, *_rest in items:
-            host[pos:pos + im.size] = im.reshape(-1)
-            pos += im.size
+
+        def fill(host):
+            host[:desc.nbytes] = desc.view(np.uint8)
+            if lay is not None:
+                for key, at in (("rec1", "r1"), ("rec2", "r2"), ("tab", "tb")):
+                    host[lay[at]:lay[at] + lay[key].nbytes] = lay[key].view(np.uint8)
+            pos = base
+            for it in items:
+                host[pos:pos + it.pixels.size] = it.pixels.reshape(-1)
+                pos += it.pixels.size
+
         with torch.cuda.device(self.device):
-            if self._dev is None or self._dev.numel() < need:
-                self._dev = torch.empty(max(slot["host"].numel(), need), dtype=torch.uint8, device=self.device)
-            self._dev[:total].copy_(slot["host"][:total], non_blocking=True)
-            slot["event"] = torch.cuda.Event()
-            slot["event"].record()
+            dev = self._stage(total, fill, scratch=need - total, room=dbytes + B * S * S * 3)
             if lay is not None:
                 self._resize_on_device(lay, total)
-            pixels, records = self._dev[base:need], self._dev[:B * desc.itemsize]
+            pixels, records = dev[base:need], dev[:desc.nbytes]
             if self.sensor != "bayer":
                 return _lib.unprocess(pixels, records, S, seed=self.seed, flags=flags)
             if self._plane is None or self._plane.shape[0] < B:

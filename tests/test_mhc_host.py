@@ -217,6 +217,50 @@ def test_wrappers_reject_host_tensors_and_unknown_methods():
             _lib.demosaic_rects(raw, desc, method=bad)
 
 
+class _SaysDevice(torch.Tensor):
+    """A host tensor whose `device` says cuda:0: it gets the arguments before the one under test past their own device check
+    on a machine without a device (nothing is launched: the argument under test raises first)."""
+    @property
+    def device(self):
+        return torch.device("cuda:0")
+
+
+def test_every_front_end_wrapper_names_the_host_tensor_it_was_given():
+    """Each tensor argument of the seven front-end wrappers in turn is a host tensor, the others pass for device tensors:
+    AdaispError naming the wrapper, the argument and what it must be, before any device work."""
+    def u8(n):
+        return torch.zeros(n, dtype=torch.uint8)
+    plane = torch.zeros((1, 4, 4), dtype=torch.int16)
+    rec = np.zeros(1, _lib.RESIZE_DESC)
+    rec["src_h"], rec["src_w"], rec["dst_h"], rec["dst_w"] = 2, 2, 2, 2
+    f32 = torch.float32
+    calls = {
+        "unprocess": (lambda src, desc, out: _lib.unprocess(src, desc, 4, out=out),
+                      dict(src=u8(48), desc=u8(_lib.UNPROCESS_DESC.itemsize), out=torch.zeros((1, 3, 4, 4), dtype=f32))),
+        "unprocess_bayer": (lambda src, desc, out: _lib.unprocess_bayer(src, desc, 4, out=out),
+                            dict(src=u8(48), desc=u8(_lib.UNPROCESS_DESC.itemsize), out=plane.clone())),
+        "demosaic": (lambda raw, out: _lib.demosaic(raw, out=out),
+                     dict(raw=plane.clone(), out=torch.zeros((1, 3, 4, 4), dtype=f32))),
+        "demosaic_rects": (lambda raw, desc, out: _lib.demosaic_rects(raw, desc, out=out),
+                           dict(raw=plane.clone(), desc=u8(_lib.UNPROCESS_DESC.itemsize),
+                                out=torch.zeros((1, 3, 4, 4), dtype=f32))),
+        "resize_u8": (lambda src, dst, desc, tabs: _lib.resize_u8(src, dst, desc, tabs, rec),
+                      dict(src=u8(12), dst=u8(12), desc=u8(rec.nbytes), tabs=torch.zeros(8, dtype=torch.int32))),
+        "raw_load": (lambda src, desc, tabs, out: _lib.raw_load(src, desc, tabs, 4, out=out),
+                     dict(src=u8(32), desc=u8(_lib.RAW_DESC.itemsize), tabs=torch.zeros(8, dtype=torch.int32),
+                          out=torch.zeros((1, 3, 4, 4), dtype=f32))),
+        "raw_correct": (lambda src, desc, gains, out: _lib.raw_correct(src, desc, gains, out=out),
+                        dict(src=u8(32), desc=u8(_lib.RAWFIX_DESC.itemsize), gains=torch.zeros(4, dtype=f32), out=u8(32))),
+    }
+    for wrapper, (call, args) in calls.items():
+        for bad in args:
+            given = {k: v if k == bad else v.as_subclass(_SaysDevice) for k, v in args.items()}
+            with pytest.raises(_lib.AdaispError) as e:
+                call(**given)
+            text = str(e.value)
+            assert wrapper + ":" in text and f" {bad} " in text and "HIP device" in text, (wrapper, bad, text)
+
+
 # ---------------------------------------------------------------------------------------------- options
 def test_source_validates_the_demosaic(tmp_path):
     U.write_dataset(str(tmp_path), [(12, 10), (9, 14)], seed=1)
