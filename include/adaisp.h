@@ -471,6 +471,12 @@ int adaisp_policy_finish(const adaisp_policy_finish_args* args, int B, void* str
  * backward sums, weight gradients) runs in a fixed order: results are bit-reproducible run to run.
  * `workspace` keeps what backward needs (pre-BatchNorm outputs, activations, mean / rstd); `scratch` holds backward
  * temporaries. Sizes: adaisp_trunk_train_workspace_bytes / _scratch_bytes.
+ * Layout (private to the library; tests/_trunkref.py restates it to read the stages' buffers): the workspace is G equal
+ * blocks, one per instance, each holding for l = 1..4 in turn y_l [B,C[l],H_l,H_l] (H_l = 64 >> l), the activation a_l of
+ * the same shape (l < 4 only: a_4 is `feat`), then mean_l and rstd_l, C[l] floats each. The scratch is G equal blocks
+ * holding for l = 1..4 dy_l and (l < 4) da_l, shaped like y_l, then B*C[0]*64*64 floats whose head receives the first
+ * layer's state-plane gradients [B,n_state,64,64] when dimg is wanted; after the G blocks comes one region for the
+ * weight-gradient partial tiles, [chunks*G][C[l]][C[l-1]][16] of the layer that needs the most (0 if none is chunked).
  * --------------------------------------------------------------------------------------------------------- */
 #define ADAISP_TRUNK_MAX_G 2
 #define ADAISP_TRUNK_LAYERS 4
