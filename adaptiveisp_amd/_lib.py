@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_raw_load", "adaisp_raw_correct", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_augment_u8", "adaisp_raw_load", "adaisp_raw_correct", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -76,6 +76,8 @@ def load():
     sz = ctypes.c_size_t
     L.adaisp_resize_u8.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, ci, ci, vp]
     L.adaisp_resize_u8.restype = ci
+    L.adaisp_augment_u8.argtypes = [vp, sz, vp, vp, ci, vp, ci, ci, cu, vp]
+    L.adaisp_augment_u8.restype = ci
     L.adaisp_raw_load.argtypes = [vp, sz, vp, vp, sz, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
     L.adaisp_raw_load.restype = ci
     L.adaisp_raw_correct.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, vp]
@@ -484,6 +486,64 @@ def resize_u8(src, dst, desc, tabs, records):
     _check(rc, "adaisp_resize_u8")
     _wrote(dst)
     return dst
+
+
+# adaisp_augment_desc (include/adaisp.h): one 80-byte record per image
+AUGMENT_DESC = np.dtype([("src_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"),
+                         ("m", "<i8", (6,)), ("lut", "<i4"), ("reserved", "<i4")], align=True)
+assert AUGMENT_DESC.itemsize == 80
+AUGMENT_M_MAX = 2 ** 40          # |m| below it: with x, y < 2^15 the 64-bit sums cannot wrap
+
+
+def _check_augment_records(records, src_bytes, n_luts, S):
+    """What adaisp_augment_u8 would turn into an all-fill image, or a map it would wrap, is an error here."""
+    r = records
+    if np.any((r["h"] < 0) | (r["w"] < 0) | (r["top"] < 0) | (r["left"] < 0) | (r["top"] > S - r["h"].astype(np.int64))
+              | (r["left"] > S - r["w"].astype(np.int64))):
+        raise AdaispError(f"augment_u8: an image's placement does not fit the {S} x {S} frame")
+    nbytes = r["h"].astype(np.int64) * r["w"] * 3
+    if np.any(r["src_offset"] < 0) or np.any(r["src_offset"] + nbytes > src_bytes):
+        raise AdaispError(f"augment_u8: a source image lies outside src ({src_bytes} bytes)")
+    if np.any((r["lut"] < -1) | (r["lut"] >= n_luts)):
+        raise AdaispError(f"augment_u8: a table index outside [-1, {n_luts})")
+    if np.any(np.abs(r["m"]) >= AUGMENT_M_MAX):
+        raise AdaispError("augment_u8: a map entry of 2^40 or more (Q16): the 64-bit sums could wrap")
+
+
+def augment_u8(src, desc, luts, S, fill=0, out=None, records=None):
+    """adaisp_augment_u8: uint8 HWC BGR images packed in the device byte tensor `src` (any offset: a slice is fine), each
+    letterboxed into an S x S frame of colour `fill` (B | G << 8 | R << 16), warped through its Q16 inverse map and, with a
+    table, re-coloured in HSV -> uint8 [B,S,S,3] on the device. `desc`: B records of AUGMENT_DESC as a device byte tensor;
+    `luts`: the 768-byte tables (hue, saturation, value) as a device byte tensor, or None when no record names one;
+    `records` (host, optional): the same records as a numpy array, checked against the buffers before any device work.
+    `out`: any contiguous uint8 device tensor of B * S * S * 3 elements."""
+    L = load()
+    _on_device("augment_u8", src, "src", torch.uint8)
+    B, S = _records("augment_u8", desc, AUGMENT_DESC), int(S)
+    n_luts = 0
+    if luts is not None:
+        if _on_device("augment_u8", luts, "luts", torch.uint8).numel() % 768:
+            raise AdaispError(f"augment_u8: luts holds {luts.numel()} bytes, not a whole number of 768-byte tables")
+        n_luts = luts.numel() // 768
+    for t, name in ((desc, "desc"), (luts, "luts"), (out, "out")):
+        if t is not None and isinstance(t, torch.Tensor) and t.device != src.device:
+            raise AdaispError(f"augment_u8: src on {src.device}, {name} on {t.device}")
+    if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not 0 <= fill <= 0xFFFFFF:
+        raise AdaispError(f"augment_u8: fill must be one BGR triple packed in 24 bits, got {fill!r}")
+    if records is not None:
+        if not isinstance(records, np.ndarray) or records.dtype != AUGMENT_DESC or records.ndim != 1 or len(records) != B:
+            raise AdaispError(f"augment_u8: records must be a 1-D numpy array of {B} AUGMENT_DESC")
+        _check_augment_records(records, src.numel(), n_luts, S)
+    if out is None:
+        out = torch.empty((max(B, 1), max(S, 1), max(S, 1), 3), dtype=torch.uint8, device=src.device)
+    elif _on_device("augment_u8", out, "out", torch.uint8).numel() != B * S * S * 3:
+        raise AdaispError(f"augment_u8: out holds {out.numel()} bytes, {B} frames of {S} x {S} x 3 need {B * S * S * 3}")
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_augment_u8(src.data_ptr(), src.numel(), desc.data_ptr(), None if not n_luts else luts.data_ptr(),
+                                 n_luts, out.data_ptr(), B, S, int(fill), _stream())
+    _check(rc, "adaisp_augment_u8")
+    _wrote(out)
+    return out
 
 
 # adaisp_raw_desc (include/adaisp.h): one 64-byte record per plane

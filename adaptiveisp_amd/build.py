@@ -15,7 +15,7 @@ ISP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"
 
 LIBS = {
     "libadaisp.so": dict(
-        sources=["isp_pointwise.hip", "isp_conv.hip", "isp_nlm.hip", "isp_pool.hip", "isp_demosaic.hip", "isp_unprocess.hip", "isp_sensor.hip", "isp_resize.hip", "isp_raw_load.hip", "isp_raw_correct.hip", "isp_export.hip", "isp_backward.hip", "isp_backward_image.hip",
+        sources=["isp_pointwise.hip", "isp_conv.hip", "isp_nlm.hip", "isp_pool.hip", "isp_demosaic.hip", "isp_unprocess.hip", "isp_sensor.hip", "isp_resize.hip", "isp_augment.hip", "isp_raw_load.hip", "isp_raw_correct.hip", "isp_export.hip", "isp_backward.hip", "isp_backward_image.hip",
                  "isp_policy.hip", "isp_trunk_train.hip", "isp_rl_train.hip", "isp_heads_train.hip", "isp_api.hip"],
         headers=["isp_internal.h", "isp_filter_math.h", "isp_unprocess_math.h", "isp_policy_math.h", "isp_demosaic_math.h", "isp_csr.h", "../../include/adaisp.h"],
         flags=ISP_FLAGS),

@@ -40,6 +40,7 @@ XYZ2CAMS = np.array([[[1.0234, -0.2969, -0.2266], [-0.5625, 1.6328, -0.0469], [-
                      [[0.6596, -0.2079, -0.0562], [-0.4782, 1.3016, 0.1933], [-0.097, 0.1581, 0.5181]]])
 RGB2XYZ = np.array([[0.4124564, 0.3575761, 0.1804375], [0.2126729, 0.7151522, 0.0721750], [0.0193339, 0.1191920, 0.9503041]])
 PRESCALE = 0.9          # unprocess_wo_mosaic's adjust_random_brightness(image, s_range=0.9)
+AUGMENT_SEED = 0x415547  # added to a source's seed for the two random streams of its augmentation
 
 
 def sample_unprocess_params(rs, add_noise=False, brightness_range=None, noise_level=None, use_linear=False):
@@ -167,12 +168,29 @@ class ImageFolderSource:
     run's) brought to the run's black_level and white level; a sidecar's gains replace `raw_gains` for that capture.
     Without both, nothing changes: no extra launch, no extra bytes. They raise ValueError with another data_name.
 
+    augment (None, or an augment.Hyp / a dict / the path of a YAML file of one; `lod` and `coco`, either resize, either
+    sensor): the reference's augment=True branch (dataset.py:483-514) without mosaic: per image the draws of
+    augment.draw (random_perspective's affine matrix, augment_hsv's tables, the two flips), from a random.Random and a
+    np.random.RandomState of their own, seeded from the source's seed and drawn on the calling thread in delivery order;
+    the file order, the metadata draws and the noise keys of a seed stay what they are without it, and the batches are the
+    same for every worker count. The descriptors and tables ride in the batch's one H2D copy and one adaisp_augment_u8
+    launch (after adaisp_resize_u8 with resize="device") warps the letterboxed uint8 images, black around them as ever, into
+    a device scratch of B frames of S x S; the unprocess / sensor kernels then read whole frames (h = w = S at (0, 0)).
+    The labels go through augment.warp_labels; `paths` and `shapes` are unchanged. The warp comes BEFORE the sensor model
+    (the reference warps the unprocessed, noisy float image, which smears white noise into correlated noise): the
+    augmented S x S frame is the scene the sensor sees, so with add_noise or sensor="bayer" the black surround carries
+    read noise and black level like any dark region, not the exact zeros of the un-augmented letterbox pad.
+    With None nothing changes: no extra launch, no extra bytes, no extra draw. HIP devices only (RuntimeError on a CPU
+    device); data_name="raw" raises ValueError (uint16 planes are not augmented).
+
     On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` and `raw` have no CPU path and raise."""
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
                  use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host", sensor="rgb", cfa="RGGB", raw_bits=12,
-                 black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0), raw_calibration=None, raw_meta=False):
+                 black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0), raw_calibration=None, raw_meta=False,
+                 augment=None):
         from ._lib import CFA, DEMOSAIC
+        from .augment import Hyp
         from .rawcal import RawCalibration, read_sidecar, resolve
         if data_name not in ("lod", "coco", "raw"):
             raise ValueError(f"data_name must be 'lod', 'coco' or 'raw', got {data_name!r}")
@@ -202,6 +220,12 @@ class ImageFolderSource:
             if add_noise or brightness_range is not None or noise_level is not None or use_linear:
                 raise ValueError("data_name='raw' takes the captures as they are: add_noise, brightness_range, noise_level "
                                  "and use_linear belong to data_name='coco'")
+        self.augment = None if augment is None else Hyp(augment)
+        if self.augment is not None and data_name == "raw":
+            raise ValueError("data_name='raw' with augment: uint16 planes are not augmented")
+        if self.augment is not None and self.device.type != "cuda":
+            raise RuntimeError("ImageFolderSource(augment=...): the warp and the HSV tables run on the HIP device only "
+                               "(adaisp_augment_u8); there is no CPU path")
         if data_name != "raw" and (raw_calibration is not None or raw_meta):
             raise ValueError("raw_calibration and raw_meta belong to data_name='raw'")
         if isinstance(raw_calibration, (str, os.PathLike)):
@@ -253,6 +277,9 @@ class ImageFolderSource:
         self.seed = 1000 * int(seed) + int(rank)
         self.rng = random.Random(self.seed)
         self.rs = np.random.RandomState(self.seed)
+        if self.augment is not None:              # streams of their own: self.rng / self.rs draw what they draw without
+            self._aug_rng = random.Random(self.seed + AUGMENT_SEED)
+            self._aug_rs = np.random.RandomState((self.seed + AUGMENT_SEED) % 2 ** 32)
         self.indices = list(range(len(self.files)))
         self.serial = 0
         self.workers = int(workers)
@@ -285,7 +312,8 @@ class ImageFolderSource:
         bayer = f", bayer {self.cfa} {self.raw_bits}-bit black {self.black_level}" if self.sensor == "bayer" else ""
         if bayer and self.demosaic != "bilinear":
             bayer += f", {self.demosaic} demosaic"
-        return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "") + bayer
+        aug = "" if self.augment is None else f", augment ({self.augment.describe()})"
+        return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "") + bayer + aug
 
     # ------------------------------------------------------------------------------------------------------ order
     def _next_index(self):
@@ -326,7 +354,32 @@ class ImageFolderSource:
         labels, paths, shapes = [it.label for it in items], [it.path for it in items], [it.shapes for it in items]
         if self.device.type != "cuda":
             return list(self._cpu_lod(items)), labels, paths, shapes
-        return list(self._device_batch(items)), labels, paths, shapes
+        plan = None
+        if self.augment is not None:
+            plan = self._augment_plan(items)
+            labels = plan["labels"]
+        return list(self._device_batch(items, plan)), labels, paths, shapes
+
+    def _augment_plan(self, items):
+        """The host half of a batch's augmentation, no device: per item, in delivery order, augment.draw from the source's
+        two augmentation streams. Returns dict(m: int64 [B,6], the Q16 inverse maps with the flips folded in; lut: int32
+        [B], each image's table or -1; luts: uint8 [n,768]; labels: the warped [k,6] float32 rows; draws: the Draws)."""
+        from .augment import draw, fixed_inverse, warp_labels
+        S, B = self.img_size, len(items)
+        m, lut, luts, labels, draws = np.zeros((B, 6), np.int64), np.full(B, -1, np.int32), [], [], []
+        for b, it in enumerate(items):
+            d = draw(self.augment, self._aug_rng, self._aug_rs, S)
+            m[b] = fixed_inverse(d.M, d.flipud, d.fliplr, S)
+            if d.luts is not None:
+                lut[b] = len(luts)
+                luts.append(d.luts.reshape(-1))
+            lb = warp_labels(it.label[:, 1:], d.M, d.s, d.flipud, d.fliplr, S)
+            label = np.zeros((len(lb), 6), np.float32)
+            label[:, 1:] = lb
+            labels.append(label)
+            draws.append(d)
+        luts = np.stack(luts) if luts else np.zeros((0, 768), np.uint8)
+        return dict(m=m, lut=lut, luts=luts, labels=labels, draws=draws)
 
     def _cpu_lod(self, items):
         S = self.img_size
@@ -453,13 +506,20 @@ class ImageFolderSource:
             return _lib.raw_load(planes, dev[:desc.nbytes], dev[dbytes:dbytes + tab.nbytes], S, pattern=self.cfa,
                                  method=self.demosaic, black_level=self.black_level, white_level=self.white_level)
 
-    def _device_batch(self, items):
+    def _device_batch(self, items, plan=None):
+        """`plan` (of _augment_plan): the batch is augmented: its descriptors and tables are staged behind the unprocess
+        descriptors, adaisp_augment_u8 writes B whole frames into device scratch behind everything else, and the
+        unprocess descriptors describe those frames."""
         from . import _lib
         if self.data_name == "raw":
             return self._raw_batch(items)
         S, B = self.img_size, len(items)
         desc = np.zeros(B, _lib.UNPROCESS_DESC)
-        _, dbytes = _sections(0, desc.nbytes)
+        if plan is None:
+            _, dbytes = _sections(0, desc.nbytes)
+        else:
+            adesc, luts = np.zeros(B, _lib.AUGMENT_DESC), plan["luts"]
+            _, a_at, l_at, dbytes = _sections(0, desc.nbytes, adesc.nbytes, luts.nbytes)
         lay = None
         if self.resize == "device":
             lay, final = self._resize_plan(items, dbytes)
@@ -469,10 +529,15 @@ class ImageFolderSource:
                 final.append((it.pixels.shape[0], it.pixels.shape[1], off))
                 off += it.pixels.size
         for b, ((h, w, src_offset), it) in enumerate(zip(final, items)):
+            top, left = it.top, it.left
+            if plan is not None:                  # the image goes to the warp; the sensor sees the whole warped frame
+                adesc[b]["src_offset"], adesc[b]["h"], adesc[b]["w"] = src_offset, h, w
+                adesc[b]["top"], adesc[b]["left"], adesc[b]["m"], adesc[b]["lut"] = top, left, plan["m"][b], plan["lut"][b]
+                h, w, src_offset, top, left = S, S, b * S * S * 3, 0, 0
             if self.sensor == "bayer" and min(h, w) < 2:
                 raise ValueError(f"{it.path}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
             desc[b]["src_offset"], desc[b]["h"], desc[b]["w"] = src_offset, h, w
-            desc[b]["top"], desc[b]["left"], desc[b]["serial"] = it.top, it.left, self.serial
+            desc[b]["top"], desc[b]["left"], desc[b]["serial"] = top, left, self.serial
             self.serial += 1
         flags = 0
         if self.data_name == "coco":
@@ -483,9 +548,14 @@ class ImageFolderSource:
         base = dbytes if lay is None else lay["base"]                   # where the staged pixels start
         total = base + sum(it.pixels.size for it in items)
         need = total if lay is None else total + lay["s1"] + lay["s2"]
+        frames = (need + 15) // 16 * 16                                 # augmented: B whole frames, device only
+        end = need if plan is None else frames + B * S * S * 3
 
         def fill(host):
             host[:desc.nbytes] = desc.view(np.uint8)
+            if plan is not None:
+                host[a_at:a_at + adesc.nbytes] = adesc.view(np.uint8)
+                host[l_at:l_at + luts.nbytes] = luts.reshape(-1)
             if lay is not None:
                 for key, at in (("rec1", "r1"), ("rec2", "r2"), ("tab", "tb")):
                     host[lay[at]:lay[at] + lay[key].nbytes] = lay[key].view(np.uint8)
@@ -495,10 +565,14 @@ class ImageFolderSource:
                 pos += it.pixels.size
 
         with torch.cuda.device(self.device):
-            dev = self._stage(total, fill, scratch=need - total, room=dbytes + B * S * S * 3)
+            dev = self._stage(total, fill, scratch=end - total, room=dbytes + B * S * S * 3)
             if lay is not None:
                 self._resize_on_device(lay, total)
             pixels, records = dev[base:need], dev[:desc.nbytes]
+            if plan is not None:
+                pixels = _lib.augment_u8(pixels, dev[a_at:a_at + adesc.nbytes],
+                                         dev[l_at:l_at + luts.nbytes] if luts.size else None, S, fill=0,
+                                         out=dev[frames:end], records=adesc)
             if self.sensor != "bayer":
                 return _lib.unprocess(pixels, records, S, seed=self.seed, flags=flags)
             if self._plane is None or self._plane.shape[0] < B:

@@ -383,14 +383,15 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
                   add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host",
                   sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0),
-                  raw_calibration=None, raw_meta=False):
+                  raw_calibration=None, raw_meta=False, augment=None):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
     reference's unprocess options, or "raw": uint16 .npy sensor planes with `cfa` / `raw_bits` / `black_level` / `demosaic`
     / `raw_gains` / `raw_calibration` / `raw_meta`; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
     where the resample to the training size runs; `sensor` "bayer": through the simulated `cfa` / `raw_bits` /
-    `black_level` sensor and its `demosaic`, "bilinear" or "mhc"); None: SyntheticSource."""
+    `black_level` sensor and its `demosaic`, "bilinear" or "mhc"; `augment`: None, or the hyper-parameters (an augment.Hyp, a
+    dict or a YAML path) of the affine warp / HSV / flip augmentation, one HIP launch per batch); None: SyntheticSource."""
     import random
 
     from .agent import Agent
@@ -427,7 +428,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                                    brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
                                    seed=seed, rank=rank, world=world, workers=workers, resize=resize,
                                    sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level, demosaic=demosaic,
-                                   raw_gains=raw_gains, raw_calibration=raw_calibration, raw_meta=raw_meta)
+                                   raw_gains=raw_gains, raw_calibration=raw_calibration, raw_meta=raw_meta, augment=augment)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -482,6 +483,12 @@ def build_parser():
     ap.add_argument("--cfa", default="RGGB", choices=("RGGB", "GRBG", "GBRG", "BGGR"), help="bayer: colour filter array")
     ap.add_argument("--raw-bits", type=int, default=12, help="bayer: sample depth (white level 2^bits - 1)")
     ap.add_argument("--black-level", type=int, default=None, help="bayer: black level (default 2^(bits - 6))")
+    ap.add_argument("--augment", action="store_true",
+                    help="lod / coco: augment every image (affine warp, HSV jitter, flips; one HIP launch per batch, before the "
+                         "unprocess) with the reference's low-augmentation hyper-parameters")
+    ap.add_argument("--hyp", default=None, metavar="FILE",
+                    help="a YOLO hyper-parameter YAML (hsv_h, hsv_s, hsv_v, degrees, translate, scale, shear, flipud, fliplr; other "
+                         "keys are ignored); implies --augment")
     return ap
 
 
@@ -493,6 +500,17 @@ def parse_args(argv=None):
         ap.error("--data-name raw with --sensor bayer: the planes already are a sensor's")
     if a.data_name != "raw" and (a.raw_cal is not None or a.raw_dpc is not None or a.raw_meta):
         ap.error("--raw-cal / --raw-dpc / --raw-meta need --data-name raw")
+    a.augment = a.augment or a.hyp is not None
+    if a.augment and a.data is None:
+        ap.error("--augment / --hyp need --data (the synthetic source is not augmented)")
+    if a.augment and a.data_name == "raw":
+        ap.error("--augment / --hyp with --data-name raw: uint16 planes are not augmented")
+    if a.hyp is not None:
+        from .augment import Hyp
+        try:
+            a.hyp = Hyp(a.hyp)
+        except (OSError, ValueError) as e:
+            ap.error(f"--hyp {a.hyp}: {e}")
     if a.raw_dpc is not None and a.raw_dpc < 0:
         ap.error(f"--raw-dpc must be >= 0 (got {a.raw_dpc})")
     if a.data_name == "raw" and (a.add_noise or a.bri_range is not None):
@@ -544,7 +562,8 @@ def main(argv=None):
                            noise_level=a.noise_level, use_linear=a.use_linear, workers=a.data_workers, resize=a.resize,
                            sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic,
                            raw_gains=tuple(a.raw_gains),
-                           raw_calibration=calibration_from_options(a.raw_cal, a.raw_dpc, a.cfa), raw_meta=a.raw_meta)
+                           raw_calibration=calibration_from_options(a.raw_cal, a.raw_dpc, a.cfa), raw_meta=a.raw_meta,
+                           augment=(a.hyp if a.hyp is not None else {}) if a.augment else None)
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

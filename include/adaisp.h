@@ -275,6 +275,48 @@ int adaisp_resize_u8(const uint8_t* src, size_t src_bytes, uint8_t* dst, size_t 
                      void* stream);
 
 /*
+ * Training augmentation of the replay-pool input, in front of adaisp_unprocess / adaisp_unprocess_bayer: the affine warp of
+ * `random_perspective` (augmentations.py:144-193, perspective = 0) with the flips of dataset.py:505-514 folded into the
+ * map, then the HSV tables of `augment_hsv` (augmentations.py:67-80), uint8 HWC BGR -> uint8 HWC BGR, one launch per batch.
+ * (An addition: nothing that existed changed, so ADAISP_ABI_VERSION stays 9.)
+ * src: the decoded images as adaisp_unprocess reads them, packed at any byte offsets; image b is desc[b].h x desc[b].w at
+ * src + desc[b].src_offset and stands at (top, left) of an S x S letterbox frame whose other pixels are `fill` (one BGR
+ * triple: B in bits 0-7, G in 8-15, R in 16-23). dst: B frames of S x S x 3 bytes, frame b at dst + b * S * S * 3.
+ * All arithmetic is integer (64-bit sums wrap modulo 2^64), so the result is defined bit for bit. For output pixel (x, y):
+ *     fx = m0 * x + m1 * y + m2,  fy = m3 * x + m4 * y + m5        m[]: the inverse map, Q16
+ *     X = fx >> 16, Y = fy >> 16 (arithmetic shift: floor);  ax = (fx >> 11) & 31, ay = (fy >> 11) & 31
+ *     P(i, j) = the source pixel at row j - top, column i - left if that lies in [0, h) x [0, w), else fill; each of the
+ *               four taps resolved on its own
+ *     v = ((32 - ax) (32 - ay) P(X, Y) + ax (32 - ay) P(X + 1, Y) + (32 - ax) ay P(X, Y + 1) + ax ay P(X + 1, Y + 1) + 512)
+ *         >> 10, per channel
+ * Coordinates are pixel indices with no half-pixel shift (cv2.warpAffine's convention). The identity map (65536, 0, 0, 0,
+ * 65536, 0) with lut = -1 reproduces the letterboxed frame exactly.
+ * With 0 <= lut < n_luts the warped (b, g, r) then goes through table T = luts + 768 * lut; every `/` divides non-negative
+ * integers and rounds down, so (2 n + d) / (2 d) is n / d to nearest, halves up:
+ *     V = max(b, g, r), d = V - min(b, g, r);  S = 0 if V = 0, else (255 d + V / 2) / V
+ *     H = 0 if d = 0; else n = 30 (g - b) (+ 180 d if negative) when V = r, else 30 (b - r) + 60 d when V = g, else
+ *         30 (r - g) + 120 d;  H = (2 n + d) / (2 d), 180 becoming 0        (cv2.COLOR_BGR2HSV's 8-bit H in [0, 180))
+ *     H' = T[H] mod 180, S' = T[256 + S], V' = T[512 + V]
+ *     i = H' / 30, f = H' - 30 i;  p = (V' (255 - S') + 127) / 255;  q = (V' (7650 - S' f) + 3825) / 7650;
+ *     t = (V' (7650 - S' (30 - f)) + 3825) / 7650
+ *     (r, g, b) = (V', t, p), (q, V', p), (p, V', t), (p, q, V'), (t, p, V'), (V', p, q) for i = 0 .. 5
+ * Any other lut (-1 by convention) leaves the colours as they are. An image whose placement does not fit the frame, or whose
+ * pixels do not lie inside src_bytes, comes out all `fill` and is never read from. Every byte of dst is written.
+ * ADAISP_EINVAL: null src / desc / dst, null luts with n_luts > 0, n_luts < 0, B < 1, S < 1, fill > 0xFFFFFF;
+ * ADAISP_ESHAPE: B > 65535 or S > 32768; all checked before anything touches a device. No allocation, no host
+ * synchronisation: capturable in a hipGraph.
+ */
+typedef struct adaisp_augment_desc {
+    int64_t src_offset;        /* byte offset of the image's first pixel in src                                  */
+    int32_t h, w, top, left;   /* un-padded size and its placement in the S x S frame (adaisp_unprocess_desc's)  */
+    int64_t m[6];              /* Q16 inverse map: output pixel -> frame coordinates                             */
+    int32_t lut;               /* index of the image's 768-byte table in luts; -1: no colour change              */
+    int32_t reserved;
+} adaisp_augment_desc;
+int adaisp_augment_u8(const uint8_t* src, size_t src_bytes, const adaisp_augment_desc* desc, const uint8_t* luts,
+                      int n_luts, uint8_t* dst, int B, int S, unsigned fill, void* stream);
+
+/*
  * Raw-capture loader: real sensor planes -> the letterboxed [B,3,S,S] fp32 batch in one launch (demosaic, per-channel gain,
  * resample, placement). The plane is read once, 2 bytes per native pixel, and only the batch is written: the full-resolution
  * colour image never exists in memory.

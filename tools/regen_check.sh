@@ -3,17 +3,19 @@
 # the committed files under tests/golden/ (build container only: the reference does not travel to the GPU box).
 #   tools/regen_check.sh            # all generators
 #   tools/regen_check.sh td,yolo    # some of them (`imggrad`: tests/golden/gen_imggrad.py, `unprocess`: tests/golden/gen_unprocess.py,
-#                                   # `valcli`: tests/golden/gen_valcli.py, `confusion`: tests/golden/gen_confusion.py)
+#                                   # `valcli`: tests/golden/gen_valcli.py, `confusion`: tests/golden/gen_confusion.py,
+#                                   # `augment`: tests/golden/gen_augment.py)
 set -e
 cd "$(dirname "$0")/.."
 OUT=$(mktemp -d /tmp/adaisp_regen.XXXXXX)
 cp tests/golden/state_dict_keys.json "$OUT"/ 2>/dev/null || true
 ARG=",${1:-},"
-NAMES=$(echo "$ARG" | sed 's/,imggrad,/,/; s/,unprocess,/,/; s/,valcli,/,/; s/,confusion,/,/; s/^,*//; s/,*$//')
+NAMES=$(echo "$ARG" | sed 's/,imggrad,/,/; s/,unprocess,/,/; s/,valcli,/,/; s/,confusion,/,/; s/,augment,/,/; s/^,*//; s/,*$//')
 if [ -z "${1:-}" ] || [[ "$ARG" == *,imggrad,* ]]; then python tests/golden/gen_imggrad.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,unprocess,* ]]; then python tests/golden/gen_unprocess.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,valcli,* ]]; then python tests/golden/gen_valcli.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,confusion,* ]]; then python tests/golden/gen_confusion.py --out "$OUT"; fi
+if [ -z "${1:-}" ] || [[ "$ARG" == *,augment,* ]]; then python tests/golden/gen_augment.py --out "$OUT"; fi
 if [ -n "$NAMES" ]; then python tests/golden/gen_golden.py --only "$NAMES" --out "$OUT"
 elif [ -z "${1:-}" ]; then python tests/golden/gen_golden.py --out "$OUT"; fi
 python - "$OUT" <<'PY'
