@@ -25,7 +25,7 @@ ABI_VERSION = 9
 UNP_UNPROCESS = 1  # adaisp_unprocess: the unprocess_wo_mosaic chain (default: convert, u8 / 255)
 UNP_NOISE = 2      # adaisp_unprocess: + shot / read noise (needs UNP_UNPROCESS)
 
-EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_augment_u8", "adaisp_raw_load", "adaisp_raw_correct", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
+EXPORTS = ("adaisp_forward", "adaisp_forward_uniform", "adaisp_process", "adaisp_backward_params", "adaisp_backward_image", "adaisp_backward_image_workspace_bytes", "adaisp_pool64", "adaisp_pool64_backward", "adaisp_demosaic", "adaisp_unprocess", "adaisp_unprocess_bayer", "adaisp_demosaic_rects", "adaisp_demosaic_ex", "adaisp_demosaic_rects_ex", "adaisp_resize_u8", "adaisp_augment_u8", "adaisp_mosaic_u8", "adaisp_raw_load", "adaisp_raw_correct", "adaisp_export_u8", "adaisp_nlm_general", "adaisp_nlm_general_workspace_bytes", "adaisp_num_params",
            "adaisp_policy_conv", "adaisp_policy_fc1", "adaisp_policy_finish",
            "adaisp_trunk_train_fwd", "adaisp_trunk_train_bwd", "adaisp_trunk_train_workspace_bytes", "adaisp_trunk_train_scratch_bytes",
            "adaisp_critic_planes_fwd", "adaisp_critic_planes_bwd", "adaisp_td_fwd", "adaisp_td_bwd",
@@ -78,6 +78,8 @@ def load():
     L.adaisp_resize_u8.restype = ci
     L.adaisp_augment_u8.argtypes = [vp, sz, vp, vp, ci, vp, ci, ci, cu, vp]
     L.adaisp_augment_u8.restype = ci
+    L.adaisp_mosaic_u8.argtypes = [vp, sz, vp, vp, ci, vp, ci, ci, ci, vp]
+    L.adaisp_mosaic_u8.restype = ci
     L.adaisp_raw_load.argtypes = [vp, sz, vp, vp, sz, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp]
     L.adaisp_raw_load.restype = ci
     L.adaisp_raw_correct.argtypes = [vp, sz, vp, sz, vp, vp, sz, ci, vp]
@@ -542,6 +544,83 @@ def augment_u8(src, desc, luts, S, fill=0, out=None, records=None):
         rc = L.adaisp_augment_u8(src.data_ptr(), src.numel(), desc.data_ptr(), None if not n_luts else luts.data_ptr(),
                                  n_luts, out.data_ptr(), B, S, int(fill), _stream())
     _check(rc, "adaisp_augment_u8")
+    _wrote(out)
+    return out
+
+
+# adaisp_mosaic_desc (include/adaisp.h): one 448-byte record per image: 2 layers of 216 bytes, each 4 tiles of 40
+MOSAIC_TILE = np.dtype([("src_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"),
+                        ("y1", "<i4"), ("dx", "<i4"), ("dy", "<i4")], align=True)
+MOSAIC_LAYER = np.dtype([("m", "<i8", (6,)), ("fill", "<u4"), ("n_tiles", "<i4"), ("tile", MOSAIC_TILE, (4,))], align=True)
+MOSAIC_DESC = np.dtype([("layer", MOSAIC_LAYER, (2,)), ("n_layers", "<i4"), ("mix", "<i4"), ("lut", "<i4"),
+                        ("reserved", "<i4")], align=True)
+assert MOSAIC_TILE.itemsize == 40 and MOSAIC_LAYER.itemsize == 216 and MOSAIC_DESC.itemsize == 448
+MOSAIC_MIX_ONE = 65536
+
+
+def _check_mosaic_records(records, src_bytes, n_luts):
+    """What adaisp_mosaic_u8 would take into range or treat as an absent tile, or a map it would wrap, is an error here."""
+    r = records
+    if np.any((r["n_layers"] < 1) | (r["n_layers"] > 2)):
+        raise AdaispError("mosaic_u8: n_layers outside {1, 2}")
+    if np.any((r["mix"] < 0) | (r["mix"] > MOSAIC_MIX_ONE)):
+        raise AdaispError(f"mosaic_u8: mix outside [0, {MOSAIC_MIX_ONE}]")
+    if np.any((r["lut"] < -1) | (r["lut"] >= n_luts)):
+        raise AdaispError(f"mosaic_u8: a table index outside [-1, {n_luts})")
+    used = np.arange(2)[None, :] < r["n_layers"][:, None]                     # [B,2]: the layers that count
+    lay = r["layer"]
+    if np.any(used & ((lay["n_tiles"] < 0) | (lay["n_tiles"] > 4))):
+        raise AdaispError("mosaic_u8: n_tiles outside [0, 4]")
+    if np.any(used & (lay["fill"] > 0xFFFFFF)):
+        raise AdaispError("mosaic_u8: fill must be one BGR triple packed in 24 bits")
+    if np.any(used[..., None] & (np.abs(lay["m"]) >= AUGMENT_M_MAX)):
+        raise AdaispError("mosaic_u8: a map entry of 2^40 or more (Q16): the 64-bit sums could wrap")
+    t = lay["tile"]                                                           # [B,2,4]
+    live = used[..., None] & (np.arange(4)[None, None, :] < lay["n_tiles"][..., None])
+    h, w = t["h"].astype(np.int64), t["w"].astype(np.int64)
+    if np.any(live & ((h < 0) | (w < 0) | (h > 32768) | (w > 32768))):
+        raise AdaispError("mosaic_u8: a tile's source size outside [0, 32768]")
+    x0, y0, x1, y1, dx, dy = (t[k].astype(np.int64) for k in ("x0", "y0", "x1", "y1", "dx", "dy"))
+    if np.any(live & ((x1 < x0) | (y1 < y0) | (x0 - dx < 0) | (x1 - dx > w) | (y0 - dy < 0) | (y1 - dy > h))):
+        raise AdaispError("mosaic_u8: a tile's rectangle maps outside its own source")
+    if np.any(live & ((t["src_offset"] < 0) | (t["src_offset"] + h * w * 3 > src_bytes))):
+        raise AdaispError(f"mosaic_u8: a tile's source lies outside src ({src_bytes} bytes)")
+
+
+def mosaic_u8(src, desc, luts, S, n_layers=2, out=None, records=None):
+    """adaisp_mosaic_u8: per image 1 or 2 layers, each a Q16 inverse map over a canvas of up to 4 tiles (uint8 HWC BGR
+    sources packed in the device byte tensor `src`, any offset) and a fill; two layers are blended with the record's Q16
+    `mix`; then the image's table -> uint8 [B,S,S,3] on the device. `desc`: B records of MOSAIC_DESC as a device byte
+    tensor; `luts` as augment_u8's; `n_layers`: 1 when no record has two layers (the second layer's code is not run at all);
+    `records` (host, optional): the same records as a numpy array, checked against the buffers before any device work (and
+    against n_layers). `out`: any contiguous uint8 device tensor of B * S * S * 3 elements."""
+    L = load()
+    _on_device("mosaic_u8", src, "src", torch.uint8)
+    B, S = _records("mosaic_u8", desc, MOSAIC_DESC), int(S)
+    n_luts = 0
+    if luts is not None:
+        if _on_device("mosaic_u8", luts, "luts", torch.uint8).numel() % 768:
+            raise AdaispError(f"mosaic_u8: luts holds {luts.numel()} bytes, not a whole number of 768-byte tables")
+        n_luts = luts.numel() // 768
+    for t, name in ((desc, "desc"), (luts, "luts"), (out, "out")):
+        if t is not None and isinstance(t, torch.Tensor) and t.device != src.device:
+            raise AdaispError(f"mosaic_u8: src on {src.device}, {name} on {t.device}")
+    if isinstance(n_layers, bool) or not isinstance(n_layers, (int, np.integer)) or n_layers not in (1, 2):
+        raise AdaispError(f"mosaic_u8: n_layers must be 1 or 2, got {n_layers!r}")
+    if records is not None:
+        if not isinstance(records, np.ndarray) or records.dtype != MOSAIC_DESC or records.ndim != 1 or len(records) != B:
+            raise AdaispError(f"mosaic_u8: records must be a 1-D numpy array of {B} MOSAIC_DESC")
+        _check_mosaic_records(records, src.numel(), n_luts)
+        if int(records["n_layers"].max()) > n_layers:
+            raise AdaispError("mosaic_u8: a record of two layers in a launch of n_layers = 1")
+    if out is None:
+        out = torch.empty((max(B, 1), max(S, 1), max(S, 1), 3), dtype=torch.uint8, device=src.device)
+    elif _on_device("mosaic_u8", out, "out", torch.uint8).numel() != B * S * S * 3:
+        raise AdaispError(f"mosaic_u8: out holds {out.numel()} bytes, {B} frames of {S} x {S} x 3 need {B * S * S * 3}")
+    with torch.cuda.device(src.device):
+        rc = L.adaisp_mosaic_u8(src.data_ptr(), src.numel(), desc.data_ptr(), None if not n_luts else luts.data_ptr(),
+                                n_luts, out.data_ptr(), B, S, int(n_layers), _stream())
+    _check(rc, "adaisp_mosaic_u8")
     _wrote(out)
     return out
 

@@ -4,7 +4,12 @@ The random draws, the matrix and the label arithmetic are the reference's (`rand
 `box_candidates`, `xyxy2xywhn`, the two flips), in its order; the pixels are the device's: adaisp_augment_u8
 (csrc/isp_augment.hip) warps the letterboxed 8-bit frame through the Q16 inverse of the drawn matrix, with the flips
 folded in, and applies the three HSV tables, all in integer arithmetic. The warp is affine: a non-zero `perspective`
-is refused. Mosaic, mixup and copy-paste are not built."""
+is refused.
+
+Mosaic and mixup (`load_mosaic`, dataloaders.py:758-814; `mixup`, augmentations.py:289-294) are loader arguments
+(ImageFolderSource(mosaic=, mixup=)), not Hyp keys: `draw_mosaic`, `mosaic_tiles`, `mosaic_boxes` and `mix_q16` are their
+host half, adaisp_mosaic_u8 samples the four-tile canvas (and blends two of them) without ever building it. Copy-paste is not
+built: it needs segment polygons, which the loaders do not read, and is a no-op for a dataset without segments."""
 import math
 import os
 import warnings
@@ -75,13 +80,12 @@ class Draw(NamedTuple):
     luts: np.ndarray
 
 
-def draw(hyp, rng, nprs, S):
-    """The draws of one S x S image, in the reference's order: random_perspective's eight `rng.uniform` (the two
-    perspective ones are made at 0 too), augment_hsv's one `nprs.uniform(-1, 1, 3)` (not made when all three gains are 0:
-    no tables then), the two `rng.random()` of the flips. `rng`: a random.Random, `nprs`: a np.random.RandomState."""
+def _perspective(hyp, rng, S, canvas):
+    """random_perspective's eight `rng.uniform` and its M = T S R P C for a `canvas` x `canvas` input cropped to S x S
+    (canvas = S: border 0; canvas = 2 S: the mosaic's border of -S / 2). Returns (M, s)."""
     C = np.eye(3)
-    C[0, 2] = -S / 2
-    C[1, 2] = -S / 2
+    C[0, 2] = -canvas / 2
+    C[1, 2] = -canvas / 2
     P = np.eye(3)
     P[2, 0] = rng.uniform(-hyp.perspective, hyp.perspective)
     P[2, 1] = rng.uniform(-hyp.perspective, hyp.perspective)
@@ -97,7 +101,12 @@ def draw(hyp, rng, nprs, S):
     T = np.eye(3)
     T[0, 2] = rng.uniform(0.5 - hyp.translate, 0.5 + hyp.translate) * S
     T[1, 2] = rng.uniform(0.5 - hyp.translate, 0.5 + hyp.translate) * S
-    M = T @ Sh @ R @ P @ C
+    return T @ Sh @ R @ P @ C, s
+
+
+def draw_colour_flips(hyp, rng, nprs):
+    """The draws behind the warp, in the reference's order: augment_hsv's one `nprs.uniform(-1, 1, 3)` (not made when all
+    three gains are 0: no tables then), the two `rng.random()` of the flips. Returns (luts or None, flipud, fliplr)."""
     luts = None
     if hyp.hsv_h or hyp.hsv_s or hyp.hsv_v:
         r = nprs.uniform(-1, 1, 3) * [hyp.hsv_h, hyp.hsv_s, hyp.hsv_v] + 1
@@ -106,6 +115,15 @@ def draw(hyp, rng, nprs, S):
                          np.clip(x * r[2], 0, 255).astype(np.uint8)])
     flipud = rng.random() < hyp.flipud
     fliplr = rng.random() < hyp.fliplr
+    return luts, flipud, fliplr
+
+
+def draw(hyp, rng, nprs, S):
+    """The draws of one S x S image, in the reference's order: random_perspective's eight `rng.uniform` (the two
+    perspective ones are made at 0 too), augment_hsv's one `nprs.uniform(-1, 1, 3)` (not made when all three gains are 0:
+    no tables then), the two `rng.random()` of the flips. `rng`: a random.Random, `nprs`: a np.random.RandomState."""
+    M, s = _perspective(hyp, rng, S, S)
+    luts, flipud, fliplr = draw_colour_flips(hyp, rng, nprs)
     return Draw(M, s, flipud, fliplr, luts)
 
 
@@ -136,6 +154,18 @@ def warp_labels(labels, M, s, flipud, fliplr, S):
     box[:, 1] = S * (lb[:, 2] - lb[:, 4] / 2)
     box[:, 2] = S * (lb[:, 1] + lb[:, 3] / 2)
     box[:, 3] = S * (lb[:, 2] + lb[:, 4] / 2)
+    return finish_labels(warp_boxes(np.concatenate([lb[:, :1], box], 1), M, s, S), S, flipud, fliplr)
+
+
+def warp_boxes(rows, M, s, S):
+    """Rows [k,5] of class + pixel xyxy through M (random_perspective, augmentations.py:217-235): the four corners, their
+    min / max, clipped to the S x S frame; the rows `box_candidates` keeps (:297-302 against the boxes before the warp times
+    s: over 2 px a side, area ratio over 0.10, aspect under 100). Returns class + warped xyxy, float64."""
+    rows = np.array(rows, np.float64).reshape(-1, 5)
+    n = len(rows)
+    if not n:
+        return rows
+    box = rows[:, 1:]
     xy = np.ones((n * 4, 3))
     xy[:, :2] = box[:, [0, 1, 2, 3, 0, 3, 2, 1]].reshape(n * 4, 2)           # x1y1, x2y2, x1y2, x2y1
     xy = (xy @ np.asarray(M, np.float64).T)[:, :2].reshape(n, 8)
@@ -149,7 +179,14 @@ def warp_labels(labels, M, s, flipud, fliplr, S):
     w2, h2 = new[:, 2] - new[:, 0], new[:, 3] - new[:, 1]
     ar = np.maximum(w2 / (h2 + eps), h2 / (w2 + eps))
     keep = (w2 > 2) & (h2 > 2) & (w2 * h2 / (w1 * h1 + eps) > 0.10) & (ar < 100)
-    lb, new = lb[keep], new[keep].clip(0, S - 1e-3)
+    return np.concatenate([rows[keep, :1], new[keep]], 1)
+
+
+def finish_labels(rows, S, flipud, fliplr):
+    """Rows [k,5] of class + pixel xyxy in the S x S frame -> class + normalised xywh with the clip of
+    xyxy2xywhn(clip=True, eps=1e-3), then the flips (y -> 1 - y, x -> 1 - x; dataset.py:505-514)."""
+    rows = np.array(rows, np.float64).reshape(-1, 5)
+    lb, new = rows.copy(), rows[:, 1:].clip(0, S - 1e-3)
     lb[:, 1] = (new[:, 0] + new[:, 2]) / 2 / S
     lb[:, 2] = (new[:, 1] + new[:, 3]) / 2 / S
     lb[:, 3] = (new[:, 2] - new[:, 0]) / S
@@ -159,3 +196,73 @@ def warp_labels(labels, M, s, flipud, fliplr, S):
     if fliplr:
         lb[:, 1] = 1 - lb[:, 1]
     return lb
+
+
+# ------------------------------------------------------------------------------------------------- mosaic and mixup
+class MosaicDraw(NamedTuple):
+    """One four-image mosaic: the dataset indices in placement order (top left, top right, bottom left, bottom right), the
+    centre (xc, yc) on the 2S x 2S canvas, the forward matrix M (canvas pixel -> S x S output pixel, before the flips)
+    and the drawn scale s."""
+    indices: tuple
+    centre: tuple
+    M: np.ndarray
+    s: float
+
+
+def draw_mosaic(hyp, rng, nprs, S, n, index):
+    """load_mosaic's draws for image `index` of a dataset of n, from `rng` in the reference's order (dataloaders.py:762-764,
+    804-812): yc then xc, each int(uniform(S / 2, 3 S / 2)); choices(range(n), k=3); the shuffle of the four indices;
+    random_perspective's eight uniforms with border (-S / 2, -S / 2): C translates by -S, T uses width = height = S.
+    `nprs` is not drawn from (the mixup ratio and the HSV gains are the caller's draws)."""
+    yc, xc = (int(rng.uniform(S / 2, 2 * S - S / 2)) for _ in range(2))
+    indices = [index] + rng.choices(range(n), k=3)
+    rng.shuffle(indices)
+    M, s = _perspective(hyp, rng, S, 2 * S)
+    return MosaicDraw(tuple(indices), (xc, yc), M, s)
+
+
+def mosaic_tiles(sizes, centre, S):
+    """The four tiles of a mosaic as adaisp_mosaic_u8 takes them: for the (h, w) of the images in placement order and the
+    centre (xc, yc), rows (x0, y0, x1, y1, dx, dy), int64 [4,6]: the canvas rectangle `x1a, y1a, x2a, y2a` of
+    dataloaders.py:770-783 and (dx, dy) = (padw, padh) = (x1a - x1b, y1a - y1b) of :785-786."""
+    xc, yc = centre
+    out = np.zeros((4, 6), np.int64)
+    for i, (h, w) in enumerate(sizes):
+        if i == 0:                                # top left
+            x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
+            x1b, y1b = w - (x2a - x1a), h - (y2a - y1a)
+        elif i == 1:                              # top right
+            x1a, y1a, x2a, y2a = xc, max(yc - h, 0), min(xc + w, S * 2), yc
+            x1b, y1b = 0, h - (y2a - y1a)
+        elif i == 2:                              # bottom left
+            x1a, y1a, x2a, y2a = max(xc - w, 0), yc, xc, min(S * 2, yc + h)
+            x1b, y1b = w - (x2a - x1a), 0
+        else:                                     # bottom right
+            x1a, y1a, x2a, y2a = xc, yc, min(xc + w, S * 2), min(S * 2, yc + h)
+            x1b, y1b = 0, 0
+        out[i] = x1a, y1a, x2a, y2a, x1a - x1b, y1a - y1b
+    return out
+
+
+def mosaic_boxes(labels, sizes, tiles, M, s, S):
+    """The label rows of one mosaic after its warp: `labels`: per tile the image's own rows [k,5] (class, x, y, w, h
+    normalised to the image), `sizes` their (h, w), `tiles` of mosaic_tiles. Per tile xywhn2xyxy(rows, w, h, padw, padh);
+    the tiles' rows concatenated and clipped to [0, 2 S]; then warp_boxes. Returns class + pixel xyxy in the S x S frame,
+    float64: what `mixup` concatenates and finish_labels ends."""
+    rows = []
+    for lb, (h, w), t in zip(labels, sizes, tiles):
+        lb = np.array(lb, np.float64).reshape(-1, 5)
+        box = lb.copy()
+        box[:, 1] = w * (lb[:, 1] - lb[:, 3] / 2) + t[4]
+        box[:, 2] = h * (lb[:, 2] - lb[:, 4] / 2) + t[5]
+        box[:, 3] = w * (lb[:, 1] + lb[:, 3] / 2) + t[4]
+        box[:, 4] = h * (lb[:, 2] + lb[:, 4] / 2) + t[5]
+        rows.append(box)
+    rows = np.concatenate(rows) if rows else np.zeros((0, 5))
+    rows[:, 1:] = rows[:, 1:].clip(0, 2 * S)
+    return warp_boxes(rows, M, s, S)
+
+
+def mix_q16(r):
+    """The mixup ratio r = nprs.beta(32, 32) as adaisp_mosaic_u8's weight of the first mosaic: rint(65536 r)."""
+    return int(np.rint(65536.0 * r))

@@ -38,9 +38,27 @@
 // S % 4 == 0 and `dst` is 4-byte aligned, byte stores otherwise) and gathers its <= 16 source pixels with byte loads,
 // so an image may start at any byte offset of `src`; a batch's sources are a few MB and stay in the L2. The image's
 // table is copied into LDS once per workgroup (768 bytes, the only LDS).
+//
+// adaisp_mosaic_u8 is the same pass over a canvas made of several sources (load_mosaic, dataloaders.py:758-814) and the
+// blend of two such canvases (mixup, augmentations.py:289-294). An image has 1 or 2 layers; a layer is a map m[0..5], a
+// `fill` and up to 4 tiles; a tile is a source (src_offset, h, w), a half-open canvas rectangle [x0, x1) x [y0, y1) and
+// (dx, dy). fx, fy, X, Y, ax, ay and v are the layer's, by the arithmetic above, with
+//     P(i, j) = the pixel at row j - dy, column i - dx of the first tile (in index order) with x0 <= i < x1 and
+//               y0 <= j < y1, else the layer's fill; each of the four taps on its own, nothing clamped
+// so taps that straddle a seam between two tiles, or a tile and the fill, blend the two. A tile is absent (never matched,
+// never read) when h or w is outside [0, 32768], its rectangle is reversed or maps outside its own source (x0 - dx < 0, x1 - dx > w, y0 - dy < 0,
+// y1 - dy > h), or its h * w * 3 bytes do not lie inside src_bytes. n_tiles is taken into [0, 4] and mix into [0, 65536].
+// With two layers (n_layers = 2 in the record AND in the launch), v0 and v1 the two layers' values and mix in Q16:
+//     v = (mix * v0 + (65536 - mix) * v1) >> 16        per channel (rounds down, as .astype(np.uint8) does)
+// else v = v0. The tables follow as above. One layer of one tile at [left, left + w) x [top, top + h) with
+// (dx, dy) = (left, top) is adaisp_augment_u8's image, byte for byte. A numpy restatement: tests/_mosaicref.py.
+// The record (448 bytes) is uniform over a workgroup: it is read through uniform (scalar) loads, the tile scan is
+// unrolled and ends in ONE gather per tap, and the second layer's 16 gathers are skipped when the image has one layer.
 #include "isp_internal.h"
 
 static_assert(sizeof(adaisp_augment_desc) == 80, "adaisp_augment_desc is 80 bytes (adaptiveisp_amd/_lib.py)");
+static_assert(sizeof(adaisp_mosaic_tile) == 40 && sizeof(adaisp_mosaic_layer) == 216 && sizeof(adaisp_mosaic_desc) == 448,
+              "adaisp_mosaic_desc is 448 bytes: 2 layers of 216 (4 tiles of 40) (adaptiveisp_amd/_lib.py)");
 
 namespace adaisp {
 namespace {
@@ -84,60 +102,32 @@ __device__ __forceinline__ Bgr hsv_tables(Bgr c, const uint8_t* lut) {
     return o;
 }
 
+// the image's 768-byte table into LDS, by the whole workgroup (AUG_THREADS threads)
+__device__ __forceinline__ void load_table(uint8_t* lut, const uint8_t* __restrict__ t) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lut[k * AUG_THREADS + threadIdx.x] = t[k * AUG_THREADS + threadIdx.x];
+    __syncthreads();
+}
+
+__device__ __forceinline__ Bgr unpack_fill(unsigned fill) { return Bgr{fill & 255u, (fill >> 8) & 255u, (fill >> 16) & 255u}; }
+
+// the header comment's v for the Q16 position (fx, fy): P(i, j) resolves one tap
+template <class Tap>
+__device__ __forceinline__ Bgr tap_blend(uint64_t fx, uint64_t fy, Tap P) {
+    const int64_t X = (int64_t)fx >> 16, Y = (int64_t)fy >> 16;
+    const unsigned ax = (unsigned)((int64_t)fx >> 11) & 31u, ay = (unsigned)((int64_t)fy >> 11) & 31u;
+    const Bgr p00 = P(X, Y), p10 = P(X + 1, Y), p01 = P(X, Y + 1), p11 = P(X + 1, Y + 1);
+    const unsigned w00 = (32u - ax) * (32u - ay), w10 = ax * (32u - ay), w01 = (32u - ax) * ay, w11 = ax * ay;
+    Bgr v;
+    v.b = (w00 * p00.b + w10 * p10.b + w01 * p01.b + w11 * p11.b + 512u) >> 10;
+    v.g = (w00 * p00.g + w10 * p10.g + w01 * p01.g + w11 * p11.g + 512u) >> 10;
+    v.r = (w00 * p00.r + w10 * p10.r + w01 * p01.r + w11 * p11.r + 512u) >> 10;
+    return v;
+}
+
+// a lane's 4 pixels (12 bytes) to row `out`: three dword stores, or byte stores of the pixels left of S
 template <bool VEC>
-__global__ __launch_bounds__(AUG_THREADS) void k_augment_u8(const uint8_t* __restrict__ src, int64_t src_bytes,
-                                                            const adaisp_augment_desc* __restrict__ desc,
-                                                            const uint8_t* __restrict__ luts, int n_luts,
-                                                            uint8_t* __restrict__ dst, int S, int quads_per_row,
-                                                            unsigned fill) {
-    const int b = blockIdx.y;
-    const adaisp_augment_desc& d = desc[b];
-    __shared__ uint8_t lut[768];
-    const bool colour = d.lut >= 0 && d.lut < n_luts;        // uniform over the workgroup; a table outside `luts`: none
-    if (colour) {
-        const uint8_t* __restrict__ t = luts + (int64_t)d.lut * 768;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lut[k * AUG_THREADS + threadIdx.x] = t[k * AUG_THREADS + threadIdx.x];
-        __syncthreads();
-    }
-    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (q >= (long)S * quads_per_row) return;
-    const int y = (int)(q / quads_per_row), x0 = (int)(q - (long)y * quads_per_row) * 4;
-    const int h = d.h, w = d.w, top = d.top, left = d.left;
-    // a placement that does not fit the S x S frame, or pixels that do not lie inside src, are never read: all fill
-    const bool fits = h >= 0 && w >= 0 && top >= 0 && left >= 0 && top <= S - h && left <= S - w && d.src_offset >= 0 &&
-                      d.src_offset <= src_bytes - (int64_t)h * w * 3;
-    const uint8_t* __restrict__ img = src + (fits ? d.src_offset : 0);
-    const Bgr pad = {fill & 255u, (fill >> 8) & 255u, (fill >> 16) & 255u};
-    // unsigned sums: the wrap modulo 2^64 is defined, and is numpy's
-    const uint64_t m0 = (uint64_t)d.m[0], m3 = (uint64_t)d.m[3];
-    uint64_t fx = m0 * (uint64_t)x0 + (uint64_t)d.m[1] * (uint64_t)y + (uint64_t)d.m[2];
-    uint64_t fy = m3 * (uint64_t)x0 + (uint64_t)d.m[4] * (uint64_t)y + (uint64_t)d.m[5];
-
-    auto tap = [&](int64_t i, int64_t j) {
-        const int64_t ix = i - left, iy = j - top;
-        if (!fits || ix < 0 || ix >= w || iy < 0 || iy >= h) return pad;
-        const uint8_t* __restrict__ px = img + (iy * w + ix) * 3;
-        return Bgr{px[0], px[1], px[2]};
-    };
-
-    uint8_t o[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k, fx += m0, fy += m3) {
-        const int64_t X = (int64_t)fx >> 16, Y = (int64_t)fy >> 16;
-        const unsigned ax = (unsigned)((int64_t)fx >> 11) & 31u, ay = (unsigned)((int64_t)fy >> 11) & 31u;
-        const Bgr p00 = tap(X, Y), p10 = tap(X + 1, Y), p01 = tap(X, Y + 1), p11 = tap(X + 1, Y + 1);
-        const unsigned w00 = (32u - ax) * (32u - ay), w10 = ax * (32u - ay), w01 = (32u - ax) * ay, w11 = ax * ay;
-        Bgr v;
-        v.b = (w00 * p00.b + w10 * p10.b + w01 * p01.b + w11 * p11.b + 512u) >> 10;
-        v.g = (w00 * p00.g + w10 * p10.g + w01 * p01.g + w11 * p11.g + 512u) >> 10;
-        v.r = (w00 * p00.r + w10 * p10.r + w01 * p01.r + w11 * p11.r + 512u) >> 10;
-        if (colour) v = hsv_tables(v, lut);
-        o[3 * k] = (uint8_t)v.b;
-        o[3 * k + 1] = (uint8_t)v.g;
-        o[3 * k + 2] = (uint8_t)v.r;
-    }
-    uint8_t* __restrict__ out = dst + ((long)b * S * S + (long)y * S + x0) * 3;
+__device__ __forceinline__ void store_quad(uint8_t* __restrict__ out, const uint8_t (&o)[12], int x0, int S) {
     if (VEC) {
         uint32_t* __restrict__ out4 = reinterpret_cast<uint32_t*>(out);
 #pragma unroll
@@ -154,6 +144,130 @@ __global__ __launch_bounds__(AUG_THREADS) void k_augment_u8(const uint8_t* __res
             }
         }
     }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(AUG_THREADS) void k_augment_u8(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                            const adaisp_augment_desc* __restrict__ desc,
+                                                            const uint8_t* __restrict__ luts, int n_luts,
+                                                            uint8_t* __restrict__ dst, int S, int quads_per_row,
+                                                            unsigned fill) {
+    const int b = blockIdx.y;
+    const adaisp_augment_desc& d = desc[b];
+    __shared__ uint8_t lut[768];
+    const bool colour = d.lut >= 0 && d.lut < n_luts;        // uniform over the workgroup; a table outside `luts`: none
+    if (colour) load_table(lut, luts + (int64_t)d.lut * 768);
+    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (q >= (long)S * quads_per_row) return;
+    const int y = (int)(q / quads_per_row), x0 = (int)(q - (long)y * quads_per_row) * 4;
+    const int h = d.h, w = d.w, top = d.top, left = d.left;
+    // a placement that does not fit the S x S frame, or pixels that do not lie inside src, are never read: all fill
+    const bool fits = h >= 0 && w >= 0 && top >= 0 && left >= 0 && top <= S - h && left <= S - w && d.src_offset >= 0 &&
+                      d.src_offset <= src_bytes - (int64_t)h * w * 3;
+    const uint8_t* __restrict__ img = src + (fits ? d.src_offset : 0);
+    const Bgr pad = unpack_fill(fill);
+    // unsigned sums: the wrap modulo 2^64 is defined, and is numpy's
+    const uint64_t m0 = (uint64_t)d.m[0], m3 = (uint64_t)d.m[3];
+    uint64_t fx = m0 * (uint64_t)x0 + (uint64_t)d.m[1] * (uint64_t)y + (uint64_t)d.m[2];
+    uint64_t fy = m3 * (uint64_t)x0 + (uint64_t)d.m[4] * (uint64_t)y + (uint64_t)d.m[5];
+
+    auto tap = [&](int64_t i, int64_t j) {
+        const int64_t ix = i - left, iy = j - top;
+        if (!fits || ix < 0 || ix >= w || iy < 0 || iy >= h) return pad;
+        const uint8_t* __restrict__ px = img + (iy * w + ix) * 3;
+        return Bgr{px[0], px[1], px[2]};
+    };
+
+    uint8_t o[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k, fx += m0, fy += m3) {
+        Bgr v = tap_blend(fx, fy, tap);
+        if (colour) v = hsv_tables(v, lut);
+        o[3 * k] = (uint8_t)v.b;
+        o[3 * k + 1] = (uint8_t)v.g;
+        o[3 * k + 2] = (uint8_t)v.r;
+    }
+    store_quad<VEC>(dst + ((long)b * S * S + (long)y * S + x0) * 3, o, x0, S);
+}
+
+// is the tile there at all (the header comment's rule)? Uniform over the workgroup.
+__device__ __forceinline__ bool tile_present(const adaisp_mosaic_tile& t, int64_t src_bytes) {
+    const int64_t h = t.h, w = t.w;
+    return h >= 0 && w >= 0 && h <= 32768 && w <= 32768 && t.x0 <= t.x1 && t.y0 <= t.y1 && (int64_t)t.x0 - t.dx >= 0 && (int64_t)t.x1 - t.dx <= w &&
+           (int64_t)t.y0 - t.dy >= 0 && (int64_t)t.y1 - t.dy <= h && t.src_offset >= 0 &&
+           t.src_offset <= src_bytes - h * w * 3;
+}
+
+// one layer's v for the lane's pixel k: `present` has bit t set for the tiles that are there
+__device__ __forceinline__ Bgr layer_value(const adaisp_mosaic_layer& L, unsigned present, const uint8_t* __restrict__ src,
+                                           uint64_t fx, uint64_t fy) {
+    const Bgr pad = unpack_fill(L.fill);
+    return tap_blend(fx, fy, [&](int64_t i, int64_t j) {
+        int64_t at = -1;                          // scanned from the last tile down: the first that contains (i, j) wins
+#pragma unroll
+        for (int t = 3; t >= 0; --t) {
+            const adaisp_mosaic_tile& T = L.tile[t];
+            if (((present >> t) & 1u) && i >= T.x0 && i < T.x1 && j >= T.y0 && j < T.y1)
+                at = T.src_offset + ((j - T.dy) * (int64_t)T.w + (i - T.dx)) * 3;
+        }
+        if (at < 0) return pad;
+        const uint8_t* __restrict__ px = src + at;
+        return Bgr{px[0], px[1], px[2]};
+    });
+}
+
+__device__ __forceinline__ unsigned layer_tiles(const adaisp_mosaic_layer& L, int64_t src_bytes) {
+    const int n = min(max(L.n_tiles, 0), 4);
+    unsigned present = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (t < n && tile_present(L.tile[t], src_bytes)) present |= 1u << t;
+    return present;
+}
+
+// TWO: the launch has images of two layers (n_layers = 2); without it the second layer's code is not there at all
+template <bool VEC, bool TWO>
+__global__ __launch_bounds__(AUG_THREADS) void k_mosaic_u8(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                           const adaisp_mosaic_desc* __restrict__ desc,
+                                                           const uint8_t* __restrict__ luts, int n_luts,
+                                                           uint8_t* __restrict__ dst, int S, int quads_per_row) {
+    const int b = blockIdx.y;
+    const adaisp_mosaic_desc& d = desc[b];
+    __shared__ uint8_t lut[768];
+    const bool colour = d.lut >= 0 && d.lut < n_luts;
+    if (colour) load_table(lut, luts + (int64_t)d.lut * 768);
+    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (q >= (long)S * quads_per_row) return;
+    const int y = (int)(q / quads_per_row), x0 = (int)(q - (long)y * quads_per_row) * 4;
+    const adaisp_mosaic_layer &L0 = d.layer[0], &L1 = d.layer[1];
+    const bool two = TWO && d.n_layers == 2;                 // uniform over the workgroup
+    const unsigned mix = (unsigned)min(max(d.mix, 0), 65536);
+    const unsigned present0 = layer_tiles(L0, src_bytes), present1 = two ? layer_tiles(L1, src_bytes) : 0u;
+    const uint64_t a0 = (uint64_t)L0.m[0], a3 = (uint64_t)L0.m[3];
+    uint64_t fx0 = a0 * (uint64_t)x0 + (uint64_t)L0.m[1] * (uint64_t)y + (uint64_t)L0.m[2];
+    uint64_t fy0 = a3 * (uint64_t)x0 + (uint64_t)L0.m[4] * (uint64_t)y + (uint64_t)L0.m[5];
+    uint64_t b0 = 0, b3 = 0, fx1 = 0, fy1 = 0;
+    if (two) {
+        b0 = (uint64_t)L1.m[0], b3 = (uint64_t)L1.m[3];
+        fx1 = b0 * (uint64_t)x0 + (uint64_t)L1.m[1] * (uint64_t)y + (uint64_t)L1.m[2];
+        fy1 = b3 * (uint64_t)x0 + (uint64_t)L1.m[4] * (uint64_t)y + (uint64_t)L1.m[5];
+    }
+    uint8_t o[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k, fx0 += a0, fy0 += a3, fx1 += b0, fy1 += b3) {
+        Bgr v = layer_value(L0, present0, src, fx0, fy0);
+        if (two) {
+            const Bgr u = layer_value(L1, present1, src, fx1, fy1);
+            v.b = (mix * v.b + (65536u - mix) * u.b) >> 16;
+            v.g = (mix * v.g + (65536u - mix) * u.g) >> 16;
+            v.r = (mix * v.r + (65536u - mix) * u.r) >> 16;
+        }
+        if (colour) v = hsv_tables(v, lut);
+        o[3 * k] = (uint8_t)v.b;
+        o[3 * k + 1] = (uint8_t)v.g;
+        o[3 * k + 2] = (uint8_t)v.r;
+    }
+    store_quad<VEC>(dst + ((long)b * S * S + (long)y * S + x0) * 3, o, x0, S);
 }
 
 }  // namespace
@@ -177,5 +291,22 @@ extern "C" int adaisp_augment_u8(const uint8_t* src, size_t src_bytes, const ada
     else
         hipLaunchKernelGGL((k_augment_u8<false>), grid, dim3(AUG_THREADS), 0, s, src, (int64_t)src_bytes, desc, luts,
                            n_luts, dst, S, qpr, fill);
+    return hipGetLastError() == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+}
+
+extern "C" int adaisp_mosaic_u8(const uint8_t* src, size_t src_bytes, const adaisp_mosaic_desc* desc, const uint8_t* luts,
+                                int n_luts, uint8_t* dst, int B, int S, int n_layers, void* stream) {
+    using namespace adaisp;
+    if (!src || !desc || !dst || B < 1 || S < 1 || n_luts < 0 || (!luts && n_luts > 0)) return ADAISP_EINVAL;
+    if (n_layers < 1 || n_layers > 2 || src_bytes > (size_t)INT64_MAX) return ADAISP_EINVAL;
+    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.y; pixel indices fit 32 bits
+    const int qpr = (S + 3) / 4;
+    const long quads = (long)S * qpr;
+    const dim3 grid((unsigned)((quads + AUG_THREADS - 1) / AUG_THREADS), (unsigned)B);
+    const bool vec = (S % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 4 == 0);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto kernel = n_layers == 2 ? (vec ? k_mosaic_u8<true, true> : k_mosaic_u8<false, true>)
+                                      : (vec ? k_mosaic_u8<true, false> : k_mosaic_u8<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(AUG_THREADS), 0, s, src, (int64_t)src_bytes, desc, luts, n_luts, dst, S, qpr);
     return hipGetLastError() == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }

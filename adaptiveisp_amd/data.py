@@ -29,8 +29,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from .val.loader import (RAW_FORMATS, imread_bgr, letterboxed_geometry, letterboxed_labels, list_images, load_letterboxed,
-                         open_raw_plane)
+from .val.loader import (RAW_FORMATS, _label_path, imread_bgr, letterboxed_geometry, letterboxed_labels, list_images,
+                         load_image, load_letterboxed, open_raw_plane, read_labels)
 
 # random_ccm's XYZ -> camera matrices and the sRGB RGB -> XYZ matrix (isp/unprocess_np.py:5-35; Brooks et al.,
 # "Unprocessing Images for Learned Raw Denoising", CVPR 2019)
@@ -98,7 +98,10 @@ class Item(NamedTuple):
                         unpad: (h2, w2) after letterbox's (letterboxed_geometry): what the device makes of it
       data_name="raw"   pixels: the memory-mapped uint16 plane at the sensor's size; size: as for resize="device", unused
                         (there is no second pass); unpad: the (h2, w2) the plane is resampled to
-    (top, left) place the final image in the S x S frame; label is [k,6] float32 with column 0 zero."""
+    (top, left) place the final image in the S x S frame; label is [k,6] float32 with column 0 zero.
+    A mosaic tile (mosaic > 0) is load_image's output, not letterboxed: pixels as above but without letterbox's resample
+    (unpad == size with resize="device"), top = left = 0, label empty, and `native` holds the file's own rows [k,5]
+    (class, x, y, w, h normalised to the image), which load_mosaic places tile by tile."""
     pixels: np.ndarray
     top: int
     left: int
@@ -107,6 +110,24 @@ class Item(NamedTuple):
     shapes: tuple
     size: tuple = None
     unpad: tuple = None
+    native: np.ndarray = None
+
+
+class SamplePlan(NamedTuple):
+    """The draws of one delivered image of a source with mosaic > 0, made where its index is handed out: `index` the file
+    asked for; `mosaics`: () for a single letterboxed image, else one augment.MosaicDraw, or two when mixed up, with `r`
+    the mixup ratio (else None); `draw`: an augment.Draw: the whole draw of a single image, and for a mosaic the first
+    mosaic's M and s with the image's tables and flips."""
+    index: int
+    mosaics: tuple
+    r: float
+    draw: tuple
+
+
+class Sample(NamedTuple):
+    """A SamplePlan and its decoded Items: the letterboxed image, or the 4 (8) tiles in placement order."""
+    plan: SamplePlan
+    items: list
 
 
 def _sections(start, *nbytes):
@@ -183,12 +204,27 @@ class ImageFolderSource:
     With None nothing changes: no extra launch, no extra bytes, no extra draw. HIP devices only (RuntimeError on a CPU
     device); data_name="raw" raises ValueError (uint16 planes are not augmented).
 
+    mosaic, mixup (probabilities, default 0; they need `augment`, and mixup needs mosaic > 0: ValueError otherwise, and for
+    data_name="raw" or a value outside [0, 1]): the reference's `mosaic = random.random() < hyp['mosaic']` branch
+    (dataset.py:822-830). Per delivered image, from the augmentation streams and where its index is handed out (so the
+    partner images are decoded by the workers ahead of time like any other): random() < mosaic; if so augment.draw_mosaic
+    (the centre, three more indices of this rank's files, the shuffle, random_perspective's draws), random() < mixup and if
+    so randint(0, n - 1), a second draw_mosaic and the ratio beta(32, 32), then the HSV draw and the flips; if not, the
+    whole augment.draw. A tile is load_image's output (the longer side at S; with resize="device" pass 1 of the resample
+    alone). One adaisp_mosaic_u8 launch per batch samples the 2S x 2S canvases without building them and blends the mixed
+    pairs; single images ride in the same launch as one-layer, one-tile records; the records travel in the batch's one H2D
+    copy, which now carries up to 8 source images per output. The canvas and the border are black, this loader's letterbox
+    colour. Labels: augment.mosaic_boxes per mosaic, concatenated for a mixup, augment.finish_labels. `paths` are those of
+    the indices asked for, `shapes` of a mosaic is None. The sensor stages see B whole frames as after adaisp_augment_u8.
+    With mosaic = 0 nothing changes: the same draws, the same adaisp_augment_u8 launch, the same bytes. Copy-paste is not
+    built.
+
     On a CPU device `lod` is computed by torch exactly as LODImages does; `coco` and `raw` have no CPU path and raise."""
 
     def __init__(self, source, img_size, device, data_name="lod", add_noise=False, brightness_range=None, noise_level=None,
                  use_linear=False, seed=0, rank=0, world=1, workers=4, resize="host", sensor="rgb", cfa="RGGB", raw_bits=12,
                  black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0), raw_calibration=None, raw_meta=False,
-                 augment=None):
+                 augment=None, mosaic=0.0, mixup=0.0):
         from ._lib import CFA, DEMOSAIC
         from .augment import Hyp
         from .rawcal import RawCalibration, read_sidecar, resolve
@@ -221,6 +257,16 @@ class ImageFolderSource:
                 raise ValueError("data_name='raw' takes the captures as they are: add_noise, brightness_range, noise_level "
                                  "and use_linear belong to data_name='coco'")
         self.augment = None if augment is None else Hyp(augment)
+        for name, p in (("mosaic", mosaic), ("mixup", mixup)):
+            if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0 <= p <= 1:
+                raise ValueError(f"{name} must be a probability in [0, 1], got {p!r}")
+        self.mosaic, self.mixup = float(mosaic), float(mixup)
+        if self.mosaic > 0 and self.augment is None:
+            raise ValueError("mosaic needs augment (the mosaic is warped, coloured and flipped by its hyper-parameters)")
+        if self.mosaic > 0 and data_name == "raw":
+            raise ValueError("data_name='raw' with mosaic: uint16 planes are not augmented")
+        if self.mixup > 0 and not self.mosaic > 0:
+            raise ValueError("mixup needs mosaic > 0 (the reference mixes mosaics only)")
         if self.augment is not None and data_name == "raw":
             raise ValueError("data_name='raw' with augment: uint16 planes are not augmented")
         if self.augment is not None and self.device.type != "cuda":
@@ -313,6 +359,8 @@ class ImageFolderSource:
         if bayer and self.demosaic != "bilinear":
             bayer += f", {self.demosaic} demosaic"
         aug = "" if self.augment is None else f", augment ({self.augment.describe()})"
+        if self.mosaic > 0:
+            aug += f", mosaic {self.mosaic:g}" + (f", mixup {self.mixup:g}" if self.mixup > 0 else "")
         return f"{kind}: {len(self.files)} files" + (", device resize" if self.resize == "device" else "") + bayer + aug
 
     # ------------------------------------------------------------------------------------------------------ order
@@ -324,9 +372,16 @@ class ImageFolderSource:
             self.rng.shuffle(self.indices)
         return i
 
-    def _decode(self, i):
-        """File i as an Item (which says what its fields hold in each mode)."""
+    def _decode(self, i, tile=False):
+        """File i as an Item (which says what its fields hold in each mode); `tile`: as a mosaic tile."""
         path = self.files[i]
+        if tile:
+            if self.resize != "device":
+                im, size = np.ascontiguousarray(load_image(path, self.img_size, augment=False)[0]), None
+            else:
+                im = imread_bgr(path)
+                size = letterboxed_geometry(im.shape[0], im.shape[1], self.img_size)[0]
+            return Item(im, 0, 0, np.zeros((0, 6), np.float32), path, None, size, size, read_labels(_label_path(path)))
         if self.data_name != "raw" and self.resize != "device":
             im, (top, left), _, lb, shapes = load_letterboxed(path, self.img_size)
             size = unpad = None
@@ -337,6 +392,36 @@ class ImageFolderSource:
         label = np.zeros((len(lb), 6), np.float32)
         label[:, 1:] = lb
         return Item(im, top, left, label, path, shapes, size, unpad)
+
+    def _next_sample(self):
+        """mosaic > 0: the next index and the draws of its image (the class docstring's order). Returns (SamplePlan,
+        [(file index, as a tile?)] to decode)."""
+        from .augment import Draw, draw, draw_colour_flips, draw_mosaic
+        hyp, rng, nprs, S, n = self.augment, self._aug_rng, self._aug_rs, self.img_size, len(self.files)
+        i = self._next_index()
+        if not rng.random() < self.mosaic:
+            return SamplePlan(i, (), None, draw(hyp, rng, nprs, S)), [(i, False)]
+        mosaics, r = (draw_mosaic(hyp, rng, nprs, S, n, i),), None
+        if rng.random() < self.mixup:
+            mosaics += (draw_mosaic(hyp, rng, nprs, S, n, rng.randint(0, n - 1)),)
+            r = float(nprs.beta(32.0, 32.0))
+        luts, flipud, fliplr = draw_colour_flips(hyp, rng, nprs)
+        return (SamplePlan(i, mosaics, r, Draw(mosaics[0].M, mosaics[0].s, flipud, fliplr, luts)),
+                [(k, True) for mz in mosaics for k in mz.indices])
+
+    def _take_samples(self, n):
+        """mosaic > 0: the next n Samples; with workers, keeps up to 2 * n more decoding behind them."""
+        if self._pool is None:
+            out = []
+            for _ in range(n):
+                plan, jobs = self._next_sample()
+                out.append(Sample(plan, [self._decode(k, tile) for k, tile in jobs]))
+            return out
+        while len(self._ahead) < 2 * n:
+            plan, jobs = self._next_sample()
+            self._ahead.append((plan, [self._pool.submit(self._decode, k, tile) for k, tile in jobs]))
+        taken = [self._ahead.popleft() for _ in range(n)]
+        return [Sample(plan, [f.result() for f in futures]) for plan, futures in taken]
 
     def _take(self, n):
         """The next n decoded items; with workers, keeps up to 2 * n more decoding behind them."""
@@ -350,6 +435,12 @@ class ImageFolderSource:
     # ------------------------------------------------------------------------------------------------------ batches
     def get_next_batch(self, n):
         n = int(n)
+        if self.mosaic > 0:
+            samples = self._take_samples(n)
+            plan = self._mosaic_plan(samples)
+            paths = [self.files[s.plan.index] for s in samples]
+            shapes = [None if s.plan.mosaics else s.items[0].shapes for s in samples]
+            return list(self._device_batch(plan["items"], plan)), plan["labels"], paths, shapes
         items = self._take(n)
         labels, paths, shapes = [it.label for it in items], [it.path for it in items], [it.shapes for it in items]
         if self.device.type != "cuda":
@@ -380,6 +471,59 @@ class ImageFolderSource:
             draws.append(d)
         luts = np.stack(luts) if luts else np.zeros((0, 768), np.uint8)
         return dict(m=m, lut=lut, luts=luts, labels=labels, draws=draws)
+
+    def _mosaic_plan(self, samples):
+        """The host half of a batch of a source with mosaic > 0, no device: the adaisp_mosaic_u8 records of the Samples (all
+        but the tiles' src_offset, which the staging decides), their tables and labels. Returns dict(records: MOSAIC_DESC
+        [B]; n_layers: the launch's; lut: int32 [B]; luts: uint8 [n,768]; labels: the [k,6] float32 rows; items: the Items
+        to stage, flat; slots: (image, layer, tile, position in items) of every tile; plans: the SamplePlans)."""
+        from . import _lib
+        from .augment import finish_labels, fixed_inverse, mix_q16, mosaic_boxes, mosaic_tiles, warp_labels
+        S, B = self.img_size, len(samples)
+        rec = np.zeros(B, _lib.MOSAIC_DESC)
+        rec["n_layers"], rec["lut"], rec["mix"] = 1, -1, _lib.MOSAIC_MIX_ONE
+        luts, labels, items, slots = [], [], [], []
+        for b, (plan, its) in enumerate(samples):
+            d = plan.draw
+            if d.luts is not None:
+                rec[b]["lut"] = len(luts)
+                luts.append(d.luts.reshape(-1))
+            if not plan.mosaics:                  # a single image is one layer with one tile
+                it = its[0]
+                h, w = it.pixels.shape[:2] if it.unpad is None else it.unpad
+                lay = rec[b]["layer"][0]
+                lay["m"], lay["n_tiles"] = fixed_inverse(d.M, d.flipud, d.fliplr, S), 1
+                t = lay["tile"][0]
+                t["h"], t["w"], t["dx"], t["dy"] = h, w, it.left, it.top
+                t["x0"], t["y0"], t["x1"], t["y1"] = it.left, it.top, it.left + w, it.top + h
+                slots.append((b, 0, 0, len(items)))
+                items.append(it)
+                rows = warp_labels(it.label[:, 1:], d.M, d.s, d.flipud, d.fliplr, S)
+            else:
+                rec[b]["n_layers"] = len(plan.mosaics)
+                if plan.r is not None:
+                    rec[b]["mix"] = mix_q16(plan.r)
+                boxes = []
+                for l, mz in enumerate(plan.mosaics):
+                    four = its[4 * l:4 * l + 4]
+                    sizes = [tuple(it.pixels.shape[:2]) if it.size is None else tuple(it.size) for it in four]
+                    tiles = mosaic_tiles(sizes, mz.centre, S)
+                    lay = rec[b]["layer"][l]
+                    lay["m"], lay["n_tiles"] = fixed_inverse(mz.M, d.flipud, d.fliplr, S), 4
+                    for k, ((h, w), row, it) in enumerate(zip(sizes, tiles, four)):
+                        t = lay["tile"][k]
+                        t["h"], t["w"] = h, w
+                        t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = row
+                        slots.append((b, l, k, len(items)))
+                        items.append(it)
+                    boxes.append(mosaic_boxes([it.native for it in four], sizes, tiles, mz.M, mz.s, S))
+                rows = finish_labels(np.concatenate(boxes), S, d.flipud, d.fliplr)
+            label = np.zeros((len(rows), 6), np.float32)
+            label[:, 1:] = rows
+            labels.append(label)
+        luts = np.stack(luts) if luts else np.zeros((0, 768), np.uint8)
+        return dict(records=rec, n_layers=int(rec["n_layers"].max()), lut=rec["lut"].copy(), luts=luts, labels=labels,
+                    items=items, slots=slots, plans=[s.plan for s in samples])
 
     def _cpu_lod(self, items):
         S = self.img_size
@@ -509,16 +653,18 @@ class ImageFolderSource:
     def _device_batch(self, items, plan=None):
         """`plan` (of _augment_plan): the batch is augmented: its descriptors and tables are staged behind the unprocess
         descriptors, adaisp_augment_u8 writes B whole frames into device scratch behind everything else, and the
-        unprocess descriptors describe those frames."""
+        unprocess descriptors describe those frames. A plan of _mosaic_plan: the same with its records and
+        adaisp_mosaic_u8; `items` are then the sources to stage, several per frame."""
         from . import _lib
         if self.data_name == "raw":
             return self._raw_batch(items)
-        S, B = self.img_size, len(items)
+        mosaic = plan is not None and "records" in plan
+        S, B = self.img_size, len(items) if plan is None else len(plan["lut"])
         desc = np.zeros(B, _lib.UNPROCESS_DESC)
         if plan is None:
             _, dbytes = _sections(0, desc.nbytes)
         else:
-            adesc, luts = np.zeros(B, _lib.AUGMENT_DESC), plan["luts"]
+            adesc, luts = plan["records"] if mosaic else np.zeros(B, _lib.AUGMENT_DESC), plan["luts"]
             _, a_at, l_at, dbytes = _sections(0, desc.nbytes, adesc.nbytes, luts.nbytes)
         lay = None
         if self.resize == "device":
@@ -528,14 +674,20 @@ class ImageFolderSource:
             for it in items:
                 final.append((it.pixels.shape[0], it.pixels.shape[1], off))
                 off += it.pixels.size
-        for b, ((h, w, src_offset), it) in enumerate(zip(final, items)):
-            top, left = it.top, it.left
+        if mosaic:
+            where = adesc["layer"]["tile"]["src_offset"]                # a view: [B, layer, tile]
+            for b, l, t, k in plan["slots"]:
+                where[b, l, t] = final[k][2]
+        for b in range(B):
+            if not mosaic:
+                (h, w, src_offset), top, left = final[b], items[b].top, items[b].left
             if plan is not None:                  # the image goes to the warp; the sensor sees the whole warped frame
-                adesc[b]["src_offset"], adesc[b]["h"], adesc[b]["w"] = src_offset, h, w
-                adesc[b]["top"], adesc[b]["left"], adesc[b]["m"], adesc[b]["lut"] = top, left, plan["m"][b], plan["lut"][b]
+                if not mosaic:
+                    adesc[b]["src_offset"], adesc[b]["h"], adesc[b]["w"] = src_offset, h, w
+                    adesc[b]["top"], adesc[b]["left"], adesc[b]["m"], adesc[b]["lut"] = top, left, plan["m"][b], plan["lut"][b]
                 h, w, src_offset, top, left = S, S, b * S * S * 3, 0, 0
             if self.sensor == "bayer" and min(h, w) < 2:
-                raise ValueError(f"{it.path}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
+                raise ValueError(f"{items[b].path}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
             desc[b]["src_offset"], desc[b]["h"], desc[b]["w"] = src_offset, h, w
             desc[b]["top"], desc[b]["left"], desc[b]["serial"] = top, left, self.serial
             self.serial += 1
@@ -569,7 +721,11 @@ class ImageFolderSource:
             if lay is not None:
                 self._resize_on_device(lay, total)
             pixels, records = dev[base:need], dev[:desc.nbytes]
-            if plan is not None:
+            if mosaic:                            # the records' fills are 0: the canvas and the border are black
+                pixels = _lib.mosaic_u8(pixels, dev[a_at:a_at + adesc.nbytes],
+                                        dev[l_at:l_at + luts.nbytes] if luts.size else None, S, n_layers=plan["n_layers"],
+                                        out=dev[frames:end], records=adesc)
+            elif plan is not None:
                 pixels = _lib.augment_u8(pixels, dev[a_at:a_at + adesc.nbytes],
                                          dev[l_at:l_at + luts.nbytes] if luts.size else None, S, fill=0,
                                          out=dev[frames:end], records=adesc)

@@ -383,7 +383,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
                   add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host",
                   sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0),
-                  raw_calibration=None, raw_meta=False, augment=None):
+                  raw_calibration=None, raw_meta=False, augment=None, mosaic=0.0, mixup=0.0):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
@@ -391,7 +391,9 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
     / `raw_gains` / `raw_calibration` / `raw_meta`; rank r reads files[r::world]; `workers` decoding threads; `resize` "host" or "device",
     where the resample to the training size runs; `sensor` "bayer": through the simulated `cfa` / `raw_bits` /
     `black_level` sensor and its `demosaic`, "bilinear" or "mhc"; `augment`: None, or the hyper-parameters (an augment.Hyp, a
-    dict or a YAML path) of the affine warp / HSV / flip augmentation, one HIP launch per batch); None: SyntheticSource."""
+    dict or a YAML path) of the affine warp / HSV / flip augmentation, one HIP launch per batch; `mosaic`, `mixup`: with
+    `augment`, the probabilities of a four-image mosaic and of blending it with a second one, in that same launch); None:
+    SyntheticSource."""
     import random
 
     from .agent import Agent
@@ -428,7 +430,8 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                                    brightness_range=brightness_range, noise_level=noise_level, use_linear=use_linear,
                                    seed=seed, rank=rank, world=world, workers=workers, resize=resize,
                                    sensor=sensor, cfa=cfa, raw_bits=raw_bits, black_level=black_level, demosaic=demosaic,
-                                   raw_gains=raw_gains, raw_calibration=raw_calibration, raw_meta=raw_meta, augment=augment)
+                                   raw_gains=raw_gains, raw_calibration=raw_calibration, raw_meta=raw_meta, augment=augment,
+                                   mosaic=mosaic, mixup=mixup)
     if source is None:
         source = SyntheticSource((3, H, W), nc=nc, seed=1000 * seed + rank, device=device)
     replay = DeviceReplayMemory(cfg, source, batch_size, device, (3, H, W), rng=random.Random(1000 * seed + rank))
@@ -489,6 +492,11 @@ def build_parser():
     ap.add_argument("--hyp", default=None, metavar="FILE",
                     help="a YOLO hyper-parameter YAML (hsv_h, hsv_s, hsv_v, degrees, translate, scale, shear, flipud, fliplr; other "
                          "keys are ignored); implies --augment")
+    ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
+                    help="with --augment: the probability that an image is a four-image mosaic (the reference's hyp['mosaic']; "
+                         "sampled and warped in one HIP launch per batch)")
+    ap.add_argument("--mixup", type=float, default=0.0, metavar="P",
+                    help="with --mosaic: the probability that a mosaic is blended with a second one (hyp['mixup'])")
     return ap
 
 
@@ -505,6 +513,12 @@ def parse_args(argv=None):
         ap.error("--augment / --hyp need --data (the synthetic source is not augmented)")
     if a.augment and a.data_name == "raw":
         ap.error("--augment / --hyp with --data-name raw: uint16 planes are not augmented")
+    if not 0 <= a.mosaic <= 1 or not 0 <= a.mixup <= 1:
+        ap.error("--mosaic and --mixup are probabilities in [0, 1]")
+    if a.mosaic > 0 and not a.augment:
+        ap.error("--mosaic needs --augment / --hyp")
+    if a.mixup > 0 and not a.mosaic > 0:
+        ap.error("--mixup needs --mosaic")
     if a.hyp is not None:
         from .augment import Hyp
         try:
@@ -563,7 +577,8 @@ def main(argv=None):
                            sensor=a.sensor, cfa=a.cfa, raw_bits=a.raw_bits, black_level=a.black_level, demosaic=a.demosaic,
                            raw_gains=tuple(a.raw_gains),
                            raw_calibration=calibration_from_options(a.raw_cal, a.raw_dpc, a.cfa), raw_meta=a.raw_meta,
-                           augment=(a.hyp if a.hyp is not None else {}) if a.augment else None)
+                           augment=(a.hyp if a.hyp is not None else {}) if a.augment else None, mosaic=a.mosaic,
+                           mixup=a.mixup)
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

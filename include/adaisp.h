@@ -317,6 +317,61 @@ int adaisp_augment_u8(const uint8_t* src, size_t src_bytes, const adaisp_augment
                       int n_luts, uint8_t* dst, int B, int S, unsigned fill, void* stream);
 
 /*
+ * Mosaic and mixup, the other half of the reference's augment=True branch: the same pass as adaisp_augment_u8 over a canvas
+ * made of up to four sources (`load_mosaic`, dataloaders.py:758-814) and the blend of two such canvases (`mixup`,
+ * augmentations.py:289-294), uint8 HWC BGR -> uint8 HWC BGR, one launch per batch. (An addition: ADAISP_ABI_VERSION stays 9.)
+ * src, luts, n_luts, dst, B, S as adaisp_augment_u8's. desc: a DEVICE array of B records. Image b has 1 or 2 layers; a layer
+ * is a Q16 inverse map m[6] (output pixel -> canvas coordinates), a `fill` (adaisp_augment_u8's packed BGR triple; bits 24-31
+ * ignored) and its first n_tiles tiles (n_tiles taken into [0, 4]); a tile is a source image of h x w pixels at
+ * src + src_offset, a half-open rectangle [x0, x1) x [y0, y1) of the canvas and (dx, dy): canvas pixel (i, j) of the rectangle
+ * is the source's row j - dy, column i - dx. The canvas has no bounds of its own. For output pixel (x, y) and each layer:
+ *     fx, fy, X, Y, ax, ay as adaisp_augment_u8's, from the layer's m[]
+ *     P(i, j) = the source pixel of the first tile (in index order) with x0 <= i < x1 and y0 <= j < y1, else the layer's fill;
+ *               each of the four taps resolved on its own, nothing clamped: taps that straddle a seam between two tiles, or
+ *               between a tile and the fill, blend the two
+ *     v = adaisp_augment_u8's ((32 - ax) (32 - ay) P(X, Y) + ... + 512) >> 10, per channel
+ * With two layers (the record's n_layers = 2 and the launch's n_layers = 2), v0 and v1 their values and mix taken into
+ * [0, 65536]:
+ *     v = (mix * v0 + (65536 - mix) * v1) >> 16, per channel         (rounds down, as the reference's .astype(np.uint8))
+ * else v = v0 and layer 1 is not looked at. With 0 <= lut < n_luts the table chain of adaisp_augment_u8 follows.
+ * A tile is absent, never matched and never read from, when h or w lies outside [0, 32768], x1 < x0 or y1 < y0, its rectangle
+ * maps outside its own source (x0 - dx < 0, x1 - dx > w, y0 - dy < 0 or y1 - dy > h), or src_offset < 0 or
+ * src_offset + h * w * 3 > src_bytes. Every byte of dst is written.
+ * "A single image is one layer with one tile": the record with layer[0] = {m, fill, 1, {src_offset, h, w, left, top, left + w,
+ * top + h, left, top}}, n_layers = 1 and the same lut gives the frame adaisp_augment_u8 gives for an image that fits its frame,
+ * byte for byte.
+ * n_layers (the argument): the largest n_layers of the records, 1 or 2; with 1 every image is made from its layer 0 alone.
+ * ADAISP_EINVAL: null src / desc / dst, null luts with n_luts > 0, n_luts < 0, B < 1, S < 1, n_layers outside {1, 2};
+ * ADAISP_ESHAPE: B > 65535 or S > 32768; all checked before anything touches a device. The records live on the device, so
+ * their n_layers, n_tiles and mix are the caller's to check (adaptiveisp_amd/_lib.py mosaic_u8 does, on the host copy); the
+ * kernel takes them into range as said above. No allocation, no host synchronisation: capturable in a hipGraph.
+ * Byte layout (little endian, no padding): tile 40 bytes: src_offset at 0, h 8, w 12, x0 16, y0 20, x1 24, y1 28, dx 32, dy 36;
+ * layer 216 bytes: m at 0, fill 48, n_tiles 52, tile[t] at 56 + 40 t; record 448 bytes: layer[l] at 216 l, n_layers 432, mix 436,
+ * lut 440, reserved 444.
+ */
+typedef struct adaisp_mosaic_tile {
+    int64_t src_offset;        /* byte offset of the source's first pixel in src                                 */
+    int32_t h, w;              /* the source's size                                                              */
+    int32_t x0, y0, x1, y1;    /* the canvas rectangle it fills, half open                                       */
+    int32_t dx, dy;            /* source column = i - dx, source row = j - dy                                    */
+} adaisp_mosaic_tile;
+typedef struct adaisp_mosaic_layer {
+    int64_t m[6];              /* Q16 inverse map: output pixel -> canvas coordinates                            */
+    uint32_t fill;             /* the canvas where no tile is: B | G << 8 | R << 16                              */
+    int32_t n_tiles;           /* 0 .. 4                                                                         */
+    adaisp_mosaic_tile tile[4];
+} adaisp_mosaic_layer;
+typedef struct adaisp_mosaic_desc {
+    adaisp_mosaic_layer layer[2];
+    int32_t n_layers;          /* 1, or 2: layer 0 blended over layer 1                                          */
+    int32_t mix;               /* Q16 weight of layer 0, 0 .. 65536                                              */
+    int32_t lut;               /* index of the image's 768-byte table in luts; -1: no colour change              */
+    int32_t reserved;
+} adaisp_mosaic_desc;
+int adaisp_mosaic_u8(const uint8_t* src, size_t src_bytes, const adaisp_mosaic_desc* desc, const uint8_t* luts, int n_luts,
+                     uint8_t* dst, int B, int S, int n_layers, void* stream);
+
+/*
  * Raw-capture loader: real sensor planes -> the letterboxed [B,3,S,S] fp32 batch in one launch (demosaic, per-channel gain,
  * resample, placement). The plane is read once, 2 bytes per native pixel, and only the batch is written: the full-resolution
  * colour image never exists in memory.
