@@ -497,19 +497,65 @@ assert AUGMENT_DESC.itemsize == 80
 AUGMENT_M_MAX = 2 ** 40          # |m| below it: with x, y < 2^15 the 64-bit sums cannot wrap
 
 
+# ---- the rules augment and mosaic records share, on arrays of any shape; `live` masks the entries that count
+def _rule_table(what, lut, n_luts):
+    if np.any((lut < -1) | (lut >= n_luts)):
+        raise AdaispError(f"{what}: a table index outside [-1, {n_luts})")
+
+
+def _rule_map(what, m, live=True):
+    if np.any(live & (np.abs(m) >= AUGMENT_M_MAX)):
+        raise AdaispError(f"{what}: a map entry of 2^40 or more (Q16): the 64-bit sums could wrap")
+
+
+def _rule_inside(what, whose, r, src_bytes, live=True):
+    """The h * w * 3 bytes at src_offset of every record (or tile) `r` lie inside src."""
+    nbytes = r["h"].astype(np.int64) * r["w"] * 3
+    if np.any(live & ((r["src_offset"] < 0) | (r["src_offset"] + nbytes > src_bytes))):
+        raise AdaispError(f"{what}: {whose} lies outside src ({src_bytes} bytes)")
+
+
 def _check_augment_records(records, src_bytes, n_luts, S):
     """What adaisp_augment_u8 would turn into an all-fill image, or a map it would wrap, is an error here."""
     r = records
     if np.any((r["h"] < 0) | (r["w"] < 0) | (r["top"] < 0) | (r["left"] < 0) | (r["top"] > S - r["h"].astype(np.int64))
               | (r["left"] > S - r["w"].astype(np.int64))):
         raise AdaispError(f"augment_u8: an image's placement does not fit the {S} x {S} frame")
-    nbytes = r["h"].astype(np.int64) * r["w"] * 3
-    if np.any(r["src_offset"] < 0) or np.any(r["src_offset"] + nbytes > src_bytes):
-        raise AdaispError(f"augment_u8: a source image lies outside src ({src_bytes} bytes)")
-    if np.any((r["lut"] < -1) | (r["lut"] >= n_luts)):
-        raise AdaispError(f"augment_u8: a table index outside [-1, {n_luts})")
-    if np.any(np.abs(r["m"]) >= AUGMENT_M_MAX):
-        raise AdaispError("augment_u8: a map entry of 2^40 or more (Q16): the 64-bit sums could wrap")
+    _rule_inside("augment_u8", "a source image", r, src_bytes)
+    _rule_table("augment_u8", r["lut"], n_luts)
+    _rule_map("augment_u8", r["m"])
+
+
+def _warp_u8(what, dtype, check, scalar, scalar_error, src, desc, luts, S, out, records):
+    """augment_u8 and mosaic_u8: `dtype` records checked by `check(records, src_bytes, n_luts, S)`, the C entry
+    adaisp_<what> with the trailing `scalar`, which is refused with `scalar_error` when that is not None."""
+    L = load()
+    _on_device(what, src, "src", torch.uint8)
+    B, S = _records(what, desc, dtype), int(S)
+    n_luts = 0
+    if luts is not None:
+        if _on_device(what, luts, "luts", torch.uint8).numel() % 768:
+            raise AdaispError(f"{what}: luts holds {luts.numel()} bytes, not a whole number of 768-byte tables")
+        n_luts = luts.numel() // 768
+    for t, name in ((desc, "desc"), (luts, "luts"), (out, "out")):
+        if t is not None and isinstance(t, torch.Tensor) and t.device != src.device:
+            raise AdaispError(f"{what}: src on {src.device}, {name} on {t.device}")
+    if scalar_error is not None:
+        raise AdaispError(f"{what}: {scalar_error}")
+    if records is not None:
+        if not isinstance(records, np.ndarray) or records.dtype != dtype or records.ndim != 1 or len(records) != B:
+            raise AdaispError(f"{what}: records must be a 1-D numpy array of {B} {what[:-3].upper()}_DESC")
+        check(records, src.numel(), n_luts, S)
+    if out is None:
+        out = torch.empty((max(B, 1), max(S, 1), max(S, 1), 3), dtype=torch.uint8, device=src.device)
+    elif _on_device(what, out, "out", torch.uint8).numel() != B * S * S * 3:
+        raise AdaispError(f"{what}: out holds {out.numel()} bytes, {B} frames of {S} x {S} x 3 need {B * S * S * 3}")
+    with torch.cuda.device(src.device):
+        rc = getattr(L, "adaisp_" + what)(src.data_ptr(), src.numel(), desc.data_ptr(), None if not n_luts else luts.data_ptr(),
+                                          n_luts, out.data_ptr(), B, S, int(scalar), _stream())
+    _check(rc, "adaisp_" + what)
+    _wrote(out)
+    return out
 
 
 def augment_u8(src, desc, luts, S, fill=0, out=None, records=None):
@@ -519,33 +565,9 @@ def augment_u8(src, desc, luts, S, fill=0, out=None, records=None):
     `luts`: the 768-byte tables (hue, saturation, value) as a device byte tensor, or None when no record names one;
     `records` (host, optional): the same records as a numpy array, checked against the buffers before any device work.
     `out`: any contiguous uint8 device tensor of B * S * S * 3 elements."""
-    L = load()
-    _on_device("augment_u8", src, "src", torch.uint8)
-    B, S = _records("augment_u8", desc, AUGMENT_DESC), int(S)
-    n_luts = 0
-    if luts is not None:
-        if _on_device("augment_u8", luts, "luts", torch.uint8).numel() % 768:
-            raise AdaispError(f"augment_u8: luts holds {luts.numel()} bytes, not a whole number of 768-byte tables")
-        n_luts = luts.numel() // 768
-    for t, name in ((desc, "desc"), (luts, "luts"), (out, "out")):
-        if t is not None and isinstance(t, torch.Tensor) and t.device != src.device:
-            raise AdaispError(f"augment_u8: src on {src.device}, {name} on {t.device}")
-    if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not 0 <= fill <= 0xFFFFFF:
-        raise AdaispError(f"augment_u8: fill must be one BGR triple packed in 24 bits, got {fill!r}")
-    if records is not None:
-        if not isinstance(records, np.ndarray) or records.dtype != AUGMENT_DESC or records.ndim != 1 or len(records) != B:
-            raise AdaispError(f"augment_u8: records must be a 1-D numpy array of {B} AUGMENT_DESC")
-        _check_augment_records(records, src.numel(), n_luts, S)
-    if out is None:
-        out = torch.empty((max(B, 1), max(S, 1), max(S, 1), 3), dtype=torch.uint8, device=src.device)
-    elif _on_device("augment_u8", out, "out", torch.uint8).numel() != B * S * S * 3:
-        raise AdaispError(f"augment_u8: out holds {out.numel()} bytes, {B} frames of {S} x {S} x 3 need {B * S * S * 3}")
-    with torch.cuda.device(src.device):
-        rc = L.adaisp_augment_u8(src.data_ptr(), src.numel(), desc.data_ptr(), None if not n_luts else luts.data_ptr(),
-                                 n_luts, out.data_ptr(), B, S, int(fill), _stream())
-    _check(rc, "adaisp_augment_u8")
-    _wrote(out)
-    return out
+    bad = isinstance(fill, bool) or not isinstance(fill, (int, np.integer)) or not 0 <= fill <= 0xFFFFFF
+    return _warp_u8("augment_u8", AUGMENT_DESC, _check_augment_records, fill,
+                    f"fill must be one BGR triple packed in 24 bits, got {fill!r}" if bad else None, src, desc, luts, S, out, records)
 
 
 # adaisp_mosaic_desc (include/adaisp.h): one 448-byte record per image: 2 layers of 216 bytes, each 4 tiles of 40
@@ -558,23 +580,22 @@ assert MOSAIC_TILE.itemsize == 40 and MOSAIC_LAYER.itemsize == 216 and MOSAIC_DE
 MOSAIC_MIX_ONE = 65536
 
 
-def _check_mosaic_records(records, src_bytes, n_luts):
-    """What adaisp_mosaic_u8 would take into range or treat as an absent tile, or a map it would wrap, is an error here."""
+def _check_mosaic_records(records, src_bytes, n_luts, n_layers=2):
+    """What adaisp_mosaic_u8 would take into range or treat as an absent tile, or a map it would wrap, is an error here, and
+    a record of more layers than the launch's `n_layers`."""
     r = records
     if np.any((r["n_layers"] < 1) | (r["n_layers"] > 2)):
         raise AdaispError("mosaic_u8: n_layers outside {1, 2}")
     if np.any((r["mix"] < 0) | (r["mix"] > MOSAIC_MIX_ONE)):
         raise AdaispError(f"mosaic_u8: mix outside [0, {MOSAIC_MIX_ONE}]")
-    if np.any((r["lut"] < -1) | (r["lut"] >= n_luts)):
-        raise AdaispError(f"mosaic_u8: a table index outside [-1, {n_luts})")
+    _rule_table("mosaic_u8", r["lut"], n_luts)
     used = np.arange(2)[None, :] < r["n_layers"][:, None]                     # [B,2]: the layers that count
     lay = r["layer"]
     if np.any(used & ((lay["n_tiles"] < 0) | (lay["n_tiles"] > 4))):
         raise AdaispError("mosaic_u8: n_tiles outside [0, 4]")
     if np.any(used & (lay["fill"] > 0xFFFFFF)):
         raise AdaispError("mosaic_u8: fill must be one BGR triple packed in 24 bits")
-    if np.any(used[..., None] & (np.abs(lay["m"]) >= AUGMENT_M_MAX)):
-        raise AdaispError("mosaic_u8: a map entry of 2^40 or more (Q16): the 64-bit sums could wrap")
+    _rule_map("mosaic_u8", lay["m"], used[..., None])
     t = lay["tile"]                                                           # [B,2,4]
     live = used[..., None] & (np.arange(4)[None, None, :] < lay["n_tiles"][..., None])
     h, w = t["h"].astype(np.int64), t["w"].astype(np.int64)
@@ -583,8 +604,9 @@ def _check_mosaic_records(records, src_bytes, n_luts):
     x0, y0, x1, y1, dx, dy = (t[k].astype(np.int64) for k in ("x0", "y0", "x1", "y1", "dx", "dy"))
     if np.any(live & ((x1 < x0) | (y1 < y0) | (x0 - dx < 0) | (x1 - dx > w) | (y0 - dy < 0) | (y1 - dy > h))):
         raise AdaispError("mosaic_u8: a tile's rectangle maps outside its own source")
-    if np.any(live & ((t["src_offset"] < 0) | (t["src_offset"] + h * w * 3 > src_bytes))):
-        raise AdaispError(f"mosaic_u8: a tile's source lies outside src ({src_bytes} bytes)")
+    _rule_inside("mosaic_u8", "a tile's source", t, src_bytes, live)
+    if np.any(r["n_layers"] > n_layers):
+        raise AdaispError("mosaic_u8: a record of two layers in a launch of n_layers = 1")
 
 
 def mosaic_u8(src, desc, luts, S, n_layers=2, out=None, records=None):
@@ -594,35 +616,9 @@ def mosaic_u8(src, desc, luts, S, n_layers=2, out=None, records=None):
     tensor; `luts` as augment_u8's; `n_layers`: 1 when no record has two layers (the second layer's code is not run at all);
     `records` (host, optional): the same records as a numpy array, checked against the buffers before any device work (and
     against n_layers). `out`: any contiguous uint8 device tensor of B * S * S * 3 elements."""
-    L = load()
-    _on_device("mosaic_u8", src, "src", torch.uint8)
-    B, S = _records("mosaic_u8", desc, MOSAIC_DESC), int(S)
-    n_luts = 0
-    if luts is not None:
-        if _on_device("mosaic_u8", luts, "luts", torch.uint8).numel() % 768:
-            raise AdaispError(f"mosaic_u8: luts holds {luts.numel()} bytes, not a whole number of 768-byte tables")
-        n_luts = luts.numel() // 768
-    for t, name in ((desc, "desc"), (luts, "luts"), (out, "out")):
-        if t is not None and isinstance(t, torch.Tensor) and t.device != src.device:
-            raise AdaispError(f"mosaic_u8: src on {src.device}, {name} on {t.device}")
-    if isinstance(n_layers, bool) or not isinstance(n_layers, (int, np.integer)) or n_layers not in (1, 2):
-        raise AdaispError(f"mosaic_u8: n_layers must be 1 or 2, got {n_layers!r}")
-    if records is not None:
-        if not isinstance(records, np.ndarray) or records.dtype != MOSAIC_DESC or records.ndim != 1 or len(records) != B:
-            raise AdaispError(f"mosaic_u8: records must be a 1-D numpy array of {B} MOSAIC_DESC")
-        _check_mosaic_records(records, src.numel(), n_luts)
-        if int(records["n_layers"].max()) > n_layers:
-            raise AdaispError("mosaic_u8: a record of two layers in a launch of n_layers = 1")
-    if out is None:
-        out = torch.empty((max(B, 1), max(S, 1), max(S, 1), 3), dtype=torch.uint8, device=src.device)
-    elif _on_device("mosaic_u8", out, "out", torch.uint8).numel() != B * S * S * 3:
-        raise AdaispError(f"mosaic_u8: out holds {out.numel()} bytes, {B} frames of {S} x {S} x 3 need {B * S * S * 3}")
-    with torch.cuda.device(src.device):
-        rc = L.adaisp_mosaic_u8(src.data_ptr(), src.numel(), desc.data_ptr(), None if not n_luts else luts.data_ptr(),
-                                n_luts, out.data_ptr(), B, S, int(n_layers), _stream())
-    _check(rc, "adaisp_mosaic_u8")
-    _wrote(out)
-    return out
+    bad = isinstance(n_layers, bool) or not isinstance(n_layers, (int, np.integer)) or n_layers not in (1, 2)
+    return _warp_u8("mosaic_u8", MOSAIC_DESC, lambda r, nbytes, n_luts, S: _check_mosaic_records(r, nbytes, n_luts, n_layers),
+                    n_layers, f"n_layers must be 1 or 2, got {n_layers!r}" if bad else None, src, desc, luts, S, out, records)
 
 
 # adaisp_raw_desc (include/adaisp.h): one 64-byte record per plane

@@ -244,6 +244,21 @@ def mosaic_tiles(sizes, centre, S):
     return out
 
 
+def fill_mosaic_layer(layer, m, sizes, tiles):
+    """One layer of an adaisp_mosaic_u8 record (a MOSAIC_LAYER element), all but the tiles' src_offset: the Q16 map `m` of
+    fixed_inverse, and per tile its source's (h, w) from `sizes` and its row (x0, y0, x1, y1, dx, dy) of mosaic_tiles."""
+    layer["m"], layer["n_tiles"] = m, len(tiles)
+    for t, (h, w), row in zip(layer["tile"], sizes, tiles):
+        t["h"], t["w"] = h, w
+        t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = row
+
+
+def fill_single_layer(layer, m, h, w, top, left):
+    """The layer of one h x w image letterboxed at (top, left): adaisp_augment_u8's image as one tile that covers
+    [left, left + w) x [top, top + h) with (dx, dy) = (left, top)."""
+    fill_mosaic_layer(layer, m, [(h, w)], [(left, top, left + w, top + h, left, top)])
+
+
 def mosaic_boxes(labels, sizes, tiles, M, s, S):
     """The label rows of one mosaic after its warp: `labels`: per tile the image's own rows [k,5] (class, x, y, w, h
     normalised to the image), `sizes` their (h, w), `tiles` of mosaic_tiles. Per tile xywhn2xyxy(rows, w, h, padw, padh);

@@ -1,23 +1,42 @@
-// Training augmentation of the replay-pool input (include/adaisp.h, adaisp_augment_u8): decoded uint8 HWC BGR images,
-// each letterboxed at (top, left) of an S x S frame -> one uint8 HWC BGR S x S frame per image: an affine warp of the
-// letterboxed frame (random_perspective with perspective = 0, augmentations.py:144-193, and the two flips of
-// dataset.py:505-514 folded into the map), then the HSV tables of augment_hsv (augmentations.py:67-80). It runs BEFORE
-// adaisp_unprocess / adaisp_unprocess_bayer: the sensor model sees the warped 8-bit scene, so its noise stays white.
+// Training augmentation of the replay-pool input (include/adaisp.h): adaisp_augment_u8 and adaisp_mosaic_u8 are ONE pass
+// with two tap rules. Decoded uint8 HWC BGR sources anywhere in `src` -> one uint8 HWC BGR S x S frame per image: an affine
+// warp (random_perspective with perspective = 0, augmentations.py:144-193, and the two flips of dataset.py:505-514 folded
+// into the map), then the HSV tables of augment_hsv (augmentations.py:67-80). It runs BEFORE adaisp_unprocess /
+// adaisp_unprocess_bayer: the sensor model sees the warped 8-bit scene, so its noise stays white. Everything is integer
+// arithmetic; two numpy int64 restatements (tests/_augref.py, tests/_mosaicref.py) match it bit for bit.
 //
-// Everything is integer arithmetic; a numpy int64 restatement (tests/_augref.py) matches it bit for bit.
-//
-// Warp, for output pixel (x, y) and the image's inverse map m[0..5] (Q16, int64; sums wrap modulo 2^64):
+// Warp, for output pixel (x, y) and an inverse map m[0..5] (Q16, int64; sums wrap modulo 2^64):
 //     fx = m0 * x + m1 * y + m2            fy = m3 * x + m4 * y + m5
 //     X = fx >> 16, Y = fy >> 16           (arithmetic shift: floor)
 //     ax = (fx >> 11) & 31, ay = (fy >> 11) & 31                               (weights in 1/32 pixel)
-//     P(i, j) = the source pixel at row j - top, column i - left when that lies in [0, h) x [0, w), else `fill`;
-//               each of the four taps on its own
 //     v = ((32 - ax) (32 - ay) P(X, Y) + ax (32 - ay) P(X + 1, Y) + (32 - ax) ay P(X, Y + 1) + ax ay P(X + 1, Y + 1)
 //          + 512) >> 10                                                        per channel
-// Coordinates are pixel indices without a half-pixel shift (cv2.warpAffine's convention). With the identity map
-// (m = 65536, 0, 0, 0, 65536, 0) ax = ay = 0 and v = P(x, y): the letterboxed frame, byte for byte.
+// with P(i, j) the kernel's tap rule, each of the four taps on its own, nothing clamped. Coordinates are pixel indices without
+// a half-pixel shift (cv2.warpAffine's convention). With the identity map (m = 65536, 0, 0, 0, 65536, 0) v = P(x, y).
 //
-// Colour, when the image has a table (lut >= 0), on the warped 8-bit (b, g, r); every `/` is a division of
+// Tap rule of adaisp_augment_u8: an image is one source (src_offset, h, w) letterboxed at (top, left) of the S x S frame,
+// one map and the launch's `fill`:
+//     P(i, j) = the source pixel at row j - top, column i - left when that lies in [0, h) x [0, w), else `fill`
+// so the identity map gives the letterboxed frame, byte for byte. A placement that does not fit the frame, or pixels that
+// do not lie inside src_bytes, are never read: all fill.
+//
+// Tap rule of adaisp_mosaic_u8: the same over a canvas made of several sources (load_mosaic, dataloaders.py:758-814) and
+// the blend of two such canvases (mixup, augmentations.py:289-294). An image has 1 or 2 layers; a layer is a map m[0..5], a
+// `fill` and up to 4 tiles; a tile is a source (src_offset, h, w), a half-open canvas rectangle [x0, x1) x [y0, y1) and
+// (dx, dy). fx, fy, X, Y, ax, ay and v are the layer's, with
+//     P(i, j) = the pixel at row j - dy, column i - dx of the first tile (in index order) with x0 <= i < x1 and
+//               y0 <= j < y1, else the layer's fill
+// so taps that straddle a seam between two tiles, or a tile and the fill, blend the two. A tile is absent (never matched,
+// never read) when h or w is outside [0, 32768], its rectangle is reversed or maps outside its own source (x0 - dx < 0,
+// x1 - dx > w, y0 - dy < 0, y1 - dy > h), or its h * w * 3 bytes do not lie inside src_bytes. n_tiles is taken into [0, 4]
+// and mix into [0, 65536]. With two layers (n_layers = 2 in the record AND in the launch) of values v0 and v1, mix in Q16:
+//     v = (mix * v0 + (65536 - mix) * v1) >> 16        per channel (rounds down, as .astype(np.uint8) does)
+// else v = v0. One layer of one tile at [left, left + w) x [top, top + h) with (dx, dy) = (left, top) is
+// adaisp_augment_u8's image, byte for byte. The record (448 bytes) is uniform over a workgroup: it is read through uniform
+// (scalar) loads, the tile scan is unrolled and ends in ONE gather per tap, and the second layer's 16 gathers are skipped
+// when the image has one layer. adaisp_augment_u8 keeps its own rule and launch: as a one-tile mosaic it is slower.
+//
+// Colour, when the image has a table (0 <= lut < n_luts), on the warped 8-bit (b, g, r); every `/` is a division of
 // non-negative integers rounded down, so (2 n + d) / (2 d) is n / d rounded to nearest, halves up:
 //   BGR -> HSV (cv2.COLOR_BGR2HSV's 8-bit ranges: H in [0, 180), S and V in [0, 255]):
 //     V = max(b, g, r), d = V - min(b, g, r)
@@ -34,26 +53,10 @@
 //     t = (V' (7650 - S' (30 - f)) + 3825) / 7650
 //     (r, g, b) = (V', t, p), (q, V', p), (p, V', t), (p, q, V'), (t, p, V'), (V', p, q)   for i = 0 .. 5
 //
-// Mapping from the output side: a lane owns 4 consecutive pixels of one output row (12 bytes: three dword stores when
-// S % 4 == 0 and `dst` is 4-byte aligned, byte stores otherwise) and gathers its <= 16 source pixels with byte loads,
-// so an image may start at any byte offset of `src`; a batch's sources are a few MB and stay in the L2. The image's
-// table is copied into LDS once per workgroup (768 bytes, the only LDS).
-//
-// adaisp_mosaic_u8 is the same pass over a canvas made of several sources (load_mosaic, dataloaders.py:758-814) and the
-// blend of two such canvases (mixup, augmentations.py:289-294). An image has 1 or 2 layers; a layer is a map m[0..5], a
-// `fill` and up to 4 tiles; a tile is a source (src_offset, h, w), a half-open canvas rectangle [x0, x1) x [y0, y1) and
-// (dx, dy). fx, fy, X, Y, ax, ay and v are the layer's, by the arithmetic above, with
-//     P(i, j) = the pixel at row j - dy, column i - dx of the first tile (in index order) with x0 <= i < x1 and
-//               y0 <= j < y1, else the layer's fill; each of the four taps on its own, nothing clamped
-// so taps that straddle a seam between two tiles, or a tile and the fill, blend the two. A tile is absent (never matched,
-// never read) when h or w is outside [0, 32768], its rectangle is reversed or maps outside its own source (x0 - dx < 0, x1 - dx > w, y0 - dy < 0,
-// y1 - dy > h), or its h * w * 3 bytes do not lie inside src_bytes. n_tiles is taken into [0, 4] and mix into [0, 65536].
-// With two layers (n_layers = 2 in the record AND in the launch), v0 and v1 the two layers' values and mix in Q16:
-//     v = (mix * v0 + (65536 - mix) * v1) >> 16        per channel (rounds down, as .astype(np.uint8) does)
-// else v = v0. The tables follow as above. One layer of one tile at [left, left + w) x [top, top + h) with
-// (dx, dy) = (left, top) is adaisp_augment_u8's image, byte for byte. A numpy restatement: tests/_mosaicref.py.
-// The record (448 bytes) is uniform over a workgroup: it is read through uniform (scalar) loads, the tile scan is
-// unrolled and ends in ONE gather per tap, and the second layer's 16 gathers are skipped when the image has one layer.
+// Mapping from the output side (warp_quads, the body both kernels share): a lane owns 4 consecutive pixels of one output
+// row (12 bytes: three dword stores when S % 4 == 0 and `dst` is 4-byte aligned, byte stores otherwise) and gathers its
+// source pixels with byte loads, so a source may start at any byte offset of `src`; a batch's sources are a few MB and stay
+// in the L2. The image's table is copied into LDS once per workgroup (768 bytes, the only LDS).
 #include "isp_internal.h"
 
 static_assert(sizeof(adaisp_augment_desc) == 80, "adaisp_augment_desc is 80 bytes (adaptiveisp_amd/_lib.py)");
@@ -146,48 +149,67 @@ __device__ __forceinline__ void store_quad(uint8_t* __restrict__ out, const uint
     }
 }
 
+// the Q16 position (fx, fy) of a map at the lane's first pixel (x0, y); unsigned: the wrap modulo 2^64 is defined, and numpy's
+struct Q16Pos {
+    uint64_t fx = 0, fy = 0, sx = 0, sy = 0;
+    Q16Pos() = default;
+    __device__ __forceinline__ Q16Pos(const int64_t (&m)[6], int x0, int y)
+        : fx((uint64_t)m[0] * (uint64_t)x0 + (uint64_t)m[1] * (uint64_t)y + (uint64_t)m[2]),
+          fy((uint64_t)m[3] * (uint64_t)x0 + (uint64_t)m[4] * (uint64_t)y + (uint64_t)m[5]),
+          sx((uint64_t)m[0]), sy((uint64_t)m[3]) {}
+    __device__ __forceinline__ void step() { fx += sx, fy += sy; }
+};
+
+// The pass both kernels are: image blockIdx.y's table (`lut_index`; none when outside `luts`) into LDS, the lane's quad,
+// its 4 values through the table, one store. `rule(x0, y)` is the kernel's tap rule: it yields the lane's value source,
+// a callable that returns the value of the next pixel to the right at every call.
+template <bool VEC, class Rule>
+__device__ __forceinline__ void warp_quads(int lut_index, const uint8_t* __restrict__ luts, int n_luts,
+                                           uint8_t* __restrict__ dst, int S, int quads_per_row, Rule rule) {
+    __shared__ uint8_t lut[768];
+    const bool colour = lut_index >= 0 && lut_index < n_luts;        // uniform over the workgroup
+    if (colour) load_table(lut, luts + (int64_t)lut_index * 768);
+    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (q >= (long)S * quads_per_row) return;
+    const int y = (int)(q / quads_per_row), x0 = (int)(q - (long)y * quads_per_row) * 4;
+    auto value = rule(x0, y);
+    uint8_t o[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        Bgr v = value();
+        if (colour) v = hsv_tables(v, lut);
+        o[3 * k] = (uint8_t)v.b;
+        o[3 * k + 1] = (uint8_t)v.g;
+        o[3 * k + 2] = (uint8_t)v.r;
+    }
+    store_quad<VEC>(dst + ((long)blockIdx.y * S * S + (long)y * S + x0) * 3, o, x0, S);
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(AUG_THREADS) void k_augment_u8(const uint8_t* __restrict__ src, int64_t src_bytes,
                                                             const adaisp_augment_desc* __restrict__ desc,
                                                             const uint8_t* __restrict__ luts, int n_luts,
                                                             uint8_t* __restrict__ dst, int S, int quads_per_row,
                                                             unsigned fill) {
-    const int b = blockIdx.y;
-    const adaisp_augment_desc& d = desc[b];
-    __shared__ uint8_t lut[768];
-    const bool colour = d.lut >= 0 && d.lut < n_luts;        // uniform over the workgroup; a table outside `luts`: none
-    if (colour) load_table(lut, luts + (int64_t)d.lut * 768);
-    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (q >= (long)S * quads_per_row) return;
-    const int y = (int)(q / quads_per_row), x0 = (int)(q - (long)y * quads_per_row) * 4;
-    const int h = d.h, w = d.w, top = d.top, left = d.left;
-    // a placement that does not fit the S x S frame, or pixels that do not lie inside src, are never read: all fill
-    const bool fits = h >= 0 && w >= 0 && top >= 0 && left >= 0 && top <= S - h && left <= S - w && d.src_offset >= 0 &&
-                      d.src_offset <= src_bytes - (int64_t)h * w * 3;
-    const uint8_t* __restrict__ img = src + (fits ? d.src_offset : 0);
-    const Bgr pad = unpack_fill(fill);
-    // unsigned sums: the wrap modulo 2^64 is defined, and is numpy's
-    const uint64_t m0 = (uint64_t)d.m[0], m3 = (uint64_t)d.m[3];
-    uint64_t fx = m0 * (uint64_t)x0 + (uint64_t)d.m[1] * (uint64_t)y + (uint64_t)d.m[2];
-    uint64_t fy = m3 * (uint64_t)x0 + (uint64_t)d.m[4] * (uint64_t)y + (uint64_t)d.m[5];
-
-    auto tap = [&](int64_t i, int64_t j) {
-        const int64_t ix = i - left, iy = j - top;
-        if (!fits || ix < 0 || ix >= w || iy < 0 || iy >= h) return pad;
-        const uint8_t* __restrict__ px = img + (iy * w + ix) * 3;
-        return Bgr{px[0], px[1], px[2]};
-    };
-
-    uint8_t o[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k, fx += m0, fy += m3) {
-        Bgr v = tap_blend(fx, fy, tap);
-        if (colour) v = hsv_tables(v, lut);
-        o[3 * k] = (uint8_t)v.b;
-        o[3 * k + 1] = (uint8_t)v.g;
-        o[3 * k + 2] = (uint8_t)v.r;
-    }
-    store_quad<VEC>(dst + ((long)b * S * S + (long)y * S + x0) * 3, o, x0, S);
+    const adaisp_augment_desc& d = desc[blockIdx.y];
+    warp_quads<VEC>(d.lut, luts, n_luts, dst, S, quads_per_row, [&](int x0, int y) {
+        const int h = d.h, w = d.w, top = d.top, left = d.left;
+        const bool fits = h >= 0 && w >= 0 && top >= 0 && left >= 0 && top <= S - h && left <= S - w && d.src_offset >= 0 &&
+                          d.src_offset <= src_bytes - (int64_t)h * w * 3;
+        const uint8_t* __restrict__ img = src + (fits ? d.src_offset : 0);
+        const Bgr pad = unpack_fill(fill);
+        auto tap = [=](int64_t i, int64_t j) {
+            const int64_t ix = i - left, iy = j - top;
+            if (!fits || ix < 0 || ix >= w || iy < 0 || iy >= h) return pad;
+            const uint8_t* __restrict__ px = img + (iy * w + ix) * 3;
+            return Bgr{px[0], px[1], px[2]};
+        };
+        return [tap, p = Q16Pos(d.m, x0, y)]() mutable {
+            const Bgr v = tap_blend(p.fx, p.fy, tap);
+            p.step();
+            return v;
+        };
+    });
 }
 
 // is the tile there at all (the header comment's rule)? Uniform over the workgroup.
@@ -231,43 +253,39 @@ __global__ __launch_bounds__(AUG_THREADS) void k_mosaic_u8(const uint8_t* __rest
                                                            const adaisp_mosaic_desc* __restrict__ desc,
                                                            const uint8_t* __restrict__ luts, int n_luts,
                                                            uint8_t* __restrict__ dst, int S, int quads_per_row) {
-    const int b = blockIdx.y;
-    const adaisp_mosaic_desc& d = desc[b];
-    __shared__ uint8_t lut[768];
-    const bool colour = d.lut >= 0 && d.lut < n_luts;
-    if (colour) load_table(lut, luts + (int64_t)d.lut * 768);
-    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (q >= (long)S * quads_per_row) return;
-    const int y = (int)(q / quads_per_row), x0 = (int)(q - (long)y * quads_per_row) * 4;
-    const adaisp_mosaic_layer &L0 = d.layer[0], &L1 = d.layer[1];
-    const bool two = TWO && d.n_layers == 2;                 // uniform over the workgroup
-    const unsigned mix = (unsigned)min(max(d.mix, 0), 65536);
-    const unsigned present0 = layer_tiles(L0, src_bytes), present1 = two ? layer_tiles(L1, src_bytes) : 0u;
-    const uint64_t a0 = (uint64_t)L0.m[0], a3 = (uint64_t)L0.m[3];
-    uint64_t fx0 = a0 * (uint64_t)x0 + (uint64_t)L0.m[1] * (uint64_t)y + (uint64_t)L0.m[2];
-    uint64_t fy0 = a3 * (uint64_t)x0 + (uint64_t)L0.m[4] * (uint64_t)y + (uint64_t)L0.m[5];
-    uint64_t b0 = 0, b3 = 0, fx1 = 0, fy1 = 0;
-    if (two) {
-        b0 = (uint64_t)L1.m[0], b3 = (uint64_t)L1.m[3];
-        fx1 = b0 * (uint64_t)x0 + (uint64_t)L1.m[1] * (uint64_t)y + (uint64_t)L1.m[2];
-        fy1 = b3 * (uint64_t)x0 + (uint64_t)L1.m[4] * (uint64_t)y + (uint64_t)L1.m[5];
-    }
-    uint8_t o[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k, fx0 += a0, fy0 += a3, fx1 += b0, fy1 += b3) {
-        Bgr v = layer_value(L0, present0, src, fx0, fy0);
-        if (two) {
-            const Bgr u = layer_value(L1, present1, src, fx1, fy1);
-            v.b = (mix * v.b + (65536u - mix) * u.b) >> 16;
-            v.g = (mix * v.g + (65536u - mix) * u.g) >> 16;
-            v.r = (mix * v.r + (65536u - mix) * u.r) >> 16;
-        }
-        if (colour) v = hsv_tables(v, lut);
-        o[3 * k] = (uint8_t)v.b;
-        o[3 * k + 1] = (uint8_t)v.g;
-        o[3 * k + 2] = (uint8_t)v.r;
-    }
-    store_quad<VEC>(dst + ((long)b * S * S + (long)y * S + x0) * 3, o, x0, S);
+    const adaisp_mosaic_desc& d = desc[blockIdx.y];
+    warp_quads<VEC>(d.lut, luts, n_luts, dst, S, quads_per_row, [&](int x0, int y) {
+        const adaisp_mosaic_layer &L0 = d.layer[0], &L1 = d.layer[1];
+        const bool two = TWO && d.n_layers == 2;             // uniform over the workgroup
+        const unsigned mix = (unsigned)min(max(d.mix, 0), 65536);
+        const unsigned present0 = layer_tiles(L0, src_bytes), present1 = two ? layer_tiles(L1, src_bytes) : 0u;
+        return [=, &L0, &L1, p0 = Q16Pos(L0.m, x0, y), p1 = two ? Q16Pos(L1.m, x0, y) : Q16Pos()]() mutable {
+            Bgr v = layer_value(L0, present0, src, p0.fx, p0.fy);
+            if (two) {
+                const Bgr u = layer_value(L1, present1, src, p1.fx, p1.fy);
+                v.b = (mix * v.b + (65536u - mix) * u.b) >> 16;
+                v.g = (mix * v.g + (65536u - mix) * u.g) >> 16;
+                v.r = (mix * v.r + (65536u - mix) * u.r) >> 16;
+            }
+            p0.step(), p1.step();
+            return v;
+        };
+    });
+}
+
+// What the two entry points check and size alike, around the one launch that differs: `own` is the entry's own argument
+// check, `launch(grid, quads_per_row, vec)` starts its kernel (vec: dword stores).
+template <class Launch>
+int launch_quads(const void* src, size_t src_bytes, const void* desc, const void* luts, int n_luts, const void* dst, int B,
+                 int S, bool own, Launch launch) {
+    if (!src || !desc || !dst || B < 1 || S < 1 || n_luts < 0 || (!luts && n_luts > 0)) return ADAISP_EINVAL;
+    if (!own || src_bytes > (size_t)INT64_MAX) return ADAISP_EINVAL;
+    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.y; pixel indices fit 32 bits
+    const int qpr = (S + 3) / 4;
+    const long quads = (long)S * qpr;
+    launch(dim3((unsigned)((quads + AUG_THREADS - 1) / AUG_THREADS), (unsigned)B), qpr,
+           (S % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 4 == 0));
+    return hipGetLastError() == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
 }
 
 }  // namespace
@@ -277,36 +295,20 @@ extern "C" int adaisp_augment_u8(const uint8_t* src, size_t src_bytes, const ada
                                  const uint8_t* luts, int n_luts, uint8_t* dst, int B, int S, unsigned fill,
                                  void* stream) {
     using namespace adaisp;
-    if (!src || !desc || !dst || B < 1 || S < 1 || n_luts < 0 || (!luts && n_luts > 0)) return ADAISP_EINVAL;
-    if (fill > 0xFFFFFFu || src_bytes > (size_t)INT64_MAX) return ADAISP_EINVAL;
-    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.y; pixel indices fit 32 bits
-    const int qpr = (S + 3) / 4;
-    const long quads = (long)S * qpr;
-    const dim3 grid((unsigned)((quads + AUG_THREADS - 1) / AUG_THREADS), (unsigned)B);
-    const bool vec = (S % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 4 == 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vec)
-        hipLaunchKernelGGL((k_augment_u8<true>), grid, dim3(AUG_THREADS), 0, s, src, (int64_t)src_bytes, desc, luts, n_luts,
-                           dst, S, qpr, fill);
-    else
-        hipLaunchKernelGGL((k_augment_u8<false>), grid, dim3(AUG_THREADS), 0, s, src, (int64_t)src_bytes, desc, luts,
-                           n_luts, dst, S, qpr, fill);
-    return hipGetLastError() == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+    return launch_quads(src, src_bytes, desc, luts, n_luts, dst, B, S, fill <= 0xFFFFFFu, [&](dim3 grid, int qpr, bool vec) {
+        hipLaunchKernelGGL(vec ? k_augment_u8<true> : k_augment_u8<false>, grid, dim3(AUG_THREADS), 0,
+                           static_cast<hipStream_t>(stream), src, (int64_t)src_bytes, desc, luts, n_luts, dst, S, qpr, fill);
+    });
 }
 
 extern "C" int adaisp_mosaic_u8(const uint8_t* src, size_t src_bytes, const adaisp_mosaic_desc* desc, const uint8_t* luts,
                                 int n_luts, uint8_t* dst, int B, int S, int n_layers, void* stream) {
     using namespace adaisp;
-    if (!src || !desc || !dst || B < 1 || S < 1 || n_luts < 0 || (!luts && n_luts > 0)) return ADAISP_EINVAL;
-    if (n_layers < 1 || n_layers > 2 || src_bytes > (size_t)INT64_MAX) return ADAISP_EINVAL;
-    if (B > 65535 || S > 32768) return ADAISP_ESHAPE;              // grid.y; pixel indices fit 32 bits
-    const int qpr = (S + 3) / 4;
-    const long quads = (long)S * qpr;
-    const dim3 grid((unsigned)((quads + AUG_THREADS - 1) / AUG_THREADS), (unsigned)B);
-    const bool vec = (S % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 4 == 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto kernel = n_layers == 2 ? (vec ? k_mosaic_u8<true, true> : k_mosaic_u8<false, true>)
-                                      : (vec ? k_mosaic_u8<true, false> : k_mosaic_u8<false, false>);
-    hipLaunchKernelGGL(kernel, grid, dim3(AUG_THREADS), 0, s, src, (int64_t)src_bytes, desc, luts, n_luts, dst, S, qpr);
-    return hipGetLastError() == hipSuccess ? ADAISP_OK : ADAISP_ELAUNCH;
+    return launch_quads(src, src_bytes, desc, luts, n_luts, dst, B, S, n_layers == 1 || n_layers == 2,
+                        [&](dim3 grid, int qpr, bool vec) {
+        const auto kernel = n_layers == 2 ? (vec ? k_mosaic_u8<true, true> : k_mosaic_u8<false, true>)
+                                          : (vec ? k_mosaic_u8<true, false> : k_mosaic_u8<false, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(AUG_THREADS), 0, static_cast<hipStream_t>(stream), src, (int64_t)src_bytes,
+                           desc, luts, n_luts, dst, S, qpr);
+    });
 }

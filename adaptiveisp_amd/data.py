@@ -139,6 +139,21 @@ def _sections(start, *nbytes):
     return (*offsets, start)
 
 
+def _label6(rows):
+    """Label rows [k,5] as the loaders deliver them: [k,6] float32 with column 0 zero."""
+    label = np.zeros((len(rows), 6), np.float32)
+    label[:, 1:] = rows
+    return label
+
+
+def _table_index(luts, draw):
+    """The index of the Draw's tables in `luts` after appending them (768 bytes), or -1 when it has none."""
+    if draw.luts is None:
+        return -1
+    luts.append(draw.luts.reshape(-1))
+    return len(luts) - 1
+
+
 class ImageFolderSource:
     """The DeviceReplayMemory source contract over an image dataset: get_next_batch(n) -> (images [n,3,S,S] on `device`,
     labels [k,6] float32 (column 0 zero), paths, shapes), the reference's `get_next_batch_` (dataset.py:541-561).
@@ -389,9 +404,7 @@ class ImageFolderSource:
             im = open_raw_plane(path) if self.data_name == "raw" else imread_bgr(path)
             size, unpad, (top, left), frame, ratio, pad, shapes = letterboxed_geometry(im.shape[0], im.shape[1], self.img_size)
             lb = letterboxed_labels(path, size, frame, ratio, pad)
-        label = np.zeros((len(lb), 6), np.float32)
-        label[:, 1:] = lb
-        return Item(im, top, left, label, path, shapes, size, unpad)
+        return Item(im, top, left, _label6(lb), path, shapes, size, unpad)
 
     def _next_sample(self):
         """mosaic > 0: the next index and the draws of its image (the class docstring's order). Returns (SamplePlan,
@@ -454,23 +467,23 @@ class ImageFolderSource:
     def _augment_plan(self, items):
         """The host half of a batch's augmentation, no device: per item, in delivery order, augment.draw from the source's
         two augmentation streams. Returns dict(m: int64 [B,6], the Q16 inverse maps with the flips folded in; lut: int32
-        [B], each image's table or -1; luts: uint8 [n,768]; labels: the warped [k,6] float32 rows; draws: the Draws)."""
+        [B], each image's table or -1; luts: uint8 [n,768]; labels: the warped [k,6] float32 rows; draws: the Draws;
+        records: AUGMENT_DESC [B], all but src_offset, which the staging decides; slots: (image, position in items))."""
+        from . import _lib
         from .augment import draw, fixed_inverse, warp_labels
         S, B = self.img_size, len(items)
-        m, lut, luts, labels, draws = np.zeros((B, 6), np.int64), np.full(B, -1, np.int32), [], [], []
+        rec = np.zeros(B, _lib.AUGMENT_DESC)
+        luts, labels, draws = [], [], []
         for b, it in enumerate(items):
             d = draw(self.augment, self._aug_rng, self._aug_rs, S)
-            m[b] = fixed_inverse(d.M, d.flipud, d.fliplr, S)
-            if d.luts is not None:
-                lut[b] = len(luts)
-                luts.append(d.luts.reshape(-1))
-            lb = warp_labels(it.label[:, 1:], d.M, d.s, d.flipud, d.fliplr, S)
-            label = np.zeros((len(lb), 6), np.float32)
-            label[:, 1:] = lb
-            labels.append(label)
+            rec[b]["h"], rec[b]["w"] = it.pixels.shape[:2] if it.unpad is None else it.unpad
+            rec[b]["top"], rec[b]["left"], rec[b]["lut"] = it.top, it.left, _table_index(luts, d)
+            rec[b]["m"] = fixed_inverse(d.M, d.flipud, d.fliplr, S)
+            labels.append(_label6(warp_labels(it.label[:, 1:], d.M, d.s, d.flipud, d.fliplr, S)))
             draws.append(d)
         luts = np.stack(luts) if luts else np.zeros((0, 768), np.uint8)
-        return dict(m=m, lut=lut, luts=luts, labels=labels, draws=draws)
+        return dict(m=rec["m"].copy(), lut=rec["lut"].copy(), luts=luts, labels=labels, draws=draws, records=rec,
+                    slots=[(b, b) for b in range(B)])
 
     def _mosaic_plan(self, samples):
         """The host half of a batch of a source with mosaic > 0, no device: the adaisp_mosaic_u8 records of the Samples (all
@@ -478,26 +491,19 @@ class ImageFolderSource:
         [B]; n_layers: the launch's; lut: int32 [B]; luts: uint8 [n,768]; labels: the [k,6] float32 rows; items: the Items
         to stage, flat; slots: (image, layer, tile, position in items) of every tile; plans: the SamplePlans)."""
         from . import _lib
-        from .augment import finish_labels, fixed_inverse, mix_q16, mosaic_boxes, mosaic_tiles, warp_labels
+        from .augment import (fill_mosaic_layer, fill_single_layer, finish_labels, fixed_inverse, mix_q16, mosaic_boxes,
+                              mosaic_tiles, warp_labels)
         S, B = self.img_size, len(samples)
         rec = np.zeros(B, _lib.MOSAIC_DESC)
-        rec["n_layers"], rec["lut"], rec["mix"] = 1, -1, _lib.MOSAIC_MIX_ONE
+        rec["n_layers"], rec["mix"] = 1, _lib.MOSAIC_MIX_ONE
         luts, labels, items, slots = [], [], [], []
         for b, (plan, its) in enumerate(samples):
             d = plan.draw
-            if d.luts is not None:
-                rec[b]["lut"] = len(luts)
-                luts.append(d.luts.reshape(-1))
+            rec[b]["lut"] = _table_index(luts, d)
             if not plan.mosaics:                  # a single image is one layer with one tile
                 it = its[0]
                 h, w = it.pixels.shape[:2] if it.unpad is None else it.unpad
-                lay = rec[b]["layer"][0]
-                lay["m"], lay["n_tiles"] = fixed_inverse(d.M, d.flipud, d.fliplr, S), 1
-                t = lay["tile"][0]
-                t["h"], t["w"], t["dx"], t["dy"] = h, w, it.left, it.top
-                t["x0"], t["y0"], t["x1"], t["y1"] = it.left, it.top, it.left + w, it.top + h
-                slots.append((b, 0, 0, len(items)))
-                items.append(it)
+                fill_single_layer(rec[b]["layer"][0], fixed_inverse(d.M, d.flipud, d.fliplr, S), h, w, it.top, it.left)
                 rows = warp_labels(it.label[:, 1:], d.M, d.s, d.flipud, d.fliplr, S)
             else:
                 rec[b]["n_layers"] = len(plan.mosaics)
@@ -508,19 +514,13 @@ class ImageFolderSource:
                     four = its[4 * l:4 * l + 4]
                     sizes = [tuple(it.pixels.shape[:2]) if it.size is None else tuple(it.size) for it in four]
                     tiles = mosaic_tiles(sizes, mz.centre, S)
-                    lay = rec[b]["layer"][l]
-                    lay["m"], lay["n_tiles"] = fixed_inverse(mz.M, d.flipud, d.fliplr, S), 4
-                    for k, ((h, w), row, it) in enumerate(zip(sizes, tiles, four)):
-                        t = lay["tile"][k]
-                        t["h"], t["w"] = h, w
-                        t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = row
-                        slots.append((b, l, k, len(items)))
-                        items.append(it)
+                    fill_mosaic_layer(rec[b]["layer"][l], fixed_inverse(mz.M, d.flipud, d.fliplr, S), sizes, tiles)
                     boxes.append(mosaic_boxes([it.native for it in four], sizes, tiles, mz.M, mz.s, S))
                 rows = finish_labels(np.concatenate(boxes), S, d.flipud, d.fliplr)
-            label = np.zeros((len(rows), 6), np.float32)
-            label[:, 1:] = rows
-            labels.append(label)
+            for k, it in enumerate(its):          # the Items are the tiles, layer by layer
+                slots.append((b, k // 4, k % 4, len(items)))
+                items.append(it)
+            labels.append(_label6(rows))
         luts = np.stack(luts) if luts else np.zeros((0, 768), np.uint8)
         return dict(records=rec, n_layers=int(rec["n_layers"].max()), lut=rec["lut"].copy(), luts=luts, labels=labels,
                     items=items, slots=slots, plans=[s.plan for s in samples])
@@ -651,20 +651,19 @@ class ImageFolderSource:
                                  method=self.demosaic, black_level=self.black_level, white_level=self.white_level)
 
     def _device_batch(self, items, plan=None):
-        """`plan` (of _augment_plan): the batch is augmented: its descriptors and tables are staged behind the unprocess
-        descriptors, adaisp_augment_u8 writes B whole frames into device scratch behind everything else, and the
-        unprocess descriptors describe those frames. A plan of _mosaic_plan: the same with its records and
-        adaisp_mosaic_u8; `items` are then the sources to stage, several per frame."""
+        """`plan` (of _augment_plan or _mosaic_plan): the batch is augmented: the plan's records, their source offsets
+        patched in, and its tables are staged behind the unprocess descriptors, adaisp_augment_u8 (AUGMENT_DESC records) or
+        adaisp_mosaic_u8 (MOSAIC_DESC: `items` are then the sources to stage, several per frame) writes B whole frames
+        into device scratch behind everything else, and the unprocess descriptors describe those frames."""
         from . import _lib
         if self.data_name == "raw":
             return self._raw_batch(items)
-        mosaic = plan is not None and "records" in plan
         S, B = self.img_size, len(items) if plan is None else len(plan["lut"])
         desc = np.zeros(B, _lib.UNPROCESS_DESC)
         if plan is None:
             _, dbytes = _sections(0, desc.nbytes)
         else:
-            adesc, luts = plan["records"] if mosaic else np.zeros(B, _lib.AUGMENT_DESC), plan["luts"]
+            adesc, luts = plan["records"], plan["luts"]
             _, a_at, l_at, dbytes = _sections(0, desc.nbytes, adesc.nbytes, luts.nbytes)
         lay = None
         if self.resize == "device":
@@ -674,17 +673,14 @@ class ImageFolderSource:
             for it in items:
                 final.append((it.pixels.shape[0], it.pixels.shape[1], off))
                 off += it.pixels.size
-        if mosaic:
-            where = adesc["layer"]["tile"]["src_offset"]                # a view: [B, layer, tile]
-            for b, l, t, k in plan["slots"]:
-                where[b, l, t] = final[k][2]
+        if plan is not None:
+            where = (adesc if adesc.dtype == _lib.AUGMENT_DESC else adesc["layer"]["tile"])["src_offset"]      # a view
+            for *at, k in plan["slots"]:
+                where[tuple(at)] = final[k][2]
         for b in range(B):
-            if not mosaic:
+            if plan is None:
                 (h, w, src_offset), top, left = final[b], items[b].top, items[b].left
-            if plan is not None:                  # the image goes to the warp; the sensor sees the whole warped frame
-                if not mosaic:
-                    adesc[b]["src_offset"], adesc[b]["h"], adesc[b]["w"] = src_offset, h, w
-                    adesc[b]["top"], adesc[b]["left"], adesc[b]["m"], adesc[b]["lut"] = top, left, plan["m"][b], plan["lut"][b]
+            else:                                 # the images go to the warp; the sensor sees the whole warped frames
                 h, w, src_offset, top, left = S, S, b * S * S * 3, 0, 0
             if self.sensor == "bayer" and min(h, w) < 2:
                 raise ValueError(f"{items[b].path}: {h} x {w} pixels at size {S}: sensor='bayer' needs at least 2 x 2")
@@ -721,14 +717,12 @@ class ImageFolderSource:
             if lay is not None:
                 self._resize_on_device(lay, total)
             pixels, records = dev[base:need], dev[:desc.nbytes]
-            if mosaic:                            # the records' fills are 0: the canvas and the border are black
-                pixels = _lib.mosaic_u8(pixels, dev[a_at:a_at + adesc.nbytes],
-                                        dev[l_at:l_at + luts.nbytes] if luts.size else None, S, n_layers=plan["n_layers"],
-                                        out=dev[frames:end], records=adesc)
-            elif plan is not None:
-                pixels = _lib.augment_u8(pixels, dev[a_at:a_at + adesc.nbytes],
-                                         dev[l_at:l_at + luts.nbytes] if luts.size else None, S, fill=0,
-                                         out=dev[frames:end], records=adesc)
+            if plan is not None:                  # the fills are 0 either way: the canvas and the border are black
+                args = pixels, dev[a_at:a_at + adesc.nbytes], dev[l_at:l_at + luts.nbytes] if luts.size else None, S
+                if adesc.dtype == _lib.AUGMENT_DESC:
+                    pixels = _lib.augment_u8(*args, fill=0, out=dev[frames:end], records=adesc)
+                else:
+                    pixels = _lib.mosaic_u8(*args, n_layers=plan["n_layers"], out=dev[frames:end], records=adesc)
             if self.sensor != "bayer":
                 return _lib.unprocess(pixels, records, S, seed=self.seed, flags=flags)
             if self._plane is None or self._plane.shape[0] < B:

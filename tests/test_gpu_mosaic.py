@@ -15,7 +15,7 @@ import torch
 import _augref as A
 import _mosaicref as R
 from adaptiveisp_amd import _lib
-from adaptiveisp_amd.augment import fixed_inverse, mix_q16, mosaic_tiles
+from adaptiveisp_amd.augment import fill_mosaic_layer, fill_single_layer, fixed_inverse, mix_q16, mosaic_tiles
 from adaptiveisp_amd.data import ImageFolderSource
 from test_augment_host import _write_pngs, affine
 from test_gpu_augment import _launch as augment_launch, _maps, _rand_u8, _tables
@@ -60,12 +60,11 @@ class Packer:
 
 def _layer(lay, pack, imgs, centre, S, m, fill, n_tiles):
     """The first n_tiles of the four-image mosaic of `imgs` around `centre` into the layer record."""
-    lay["m"], lay["fill"], lay["n_tiles"] = m, fill, n_tiles
-    rows = mosaic_tiles([im.shape[:2] for im in imgs], centre, S)
+    sizes = [im.shape[:2] for im in imgs]
+    fill_mosaic_layer(lay, m, sizes[:n_tiles], mosaic_tiles(sizes, centre, S)[:n_tiles])
+    lay["fill"] = fill
     for k in range(n_tiles):
-        t = lay["tile"][k]
-        t["src_offset"], t["h"], t["w"] = pack.add(imgs[k]), imgs[k].shape[0], imgs[k].shape[1]
-        t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = rows[k]
+        lay["tile"][k]["src_offset"] = pack.add(imgs[k])
 
 
 def _half(S, ox=0, oy=0):
@@ -148,10 +147,8 @@ def test_one_layer_one_tile_is_adaisp_augment_u8_byte_for_byte(S):
         rec["n_layers"], rec["lut"], rec["mix"] = 1, lut, 65536
         for b, (im, (top, left)) in enumerate(zip(imgs, place)):
             lay = rec[b]["layer"][0]
-            lay["m"], lay["fill"], lay["n_tiles"] = m[b], fill, 1
-            t = lay["tile"][0]
-            t["src_offset"], t["h"], t["w"], t["dx"], t["dy"] = pack.add(im), im.shape[0], im.shape[1], left, top
-            t["x0"], t["y0"], t["x1"], t["y1"] = left, top, left + im.shape[1], top + im.shape[0]
+            fill_single_layer(lay, m[b], im.shape[0], im.shape[1], top, left)
+            lay["fill"], lay["tile"][0]["src_offset"] = fill, pack.add(im)
         pack.add(np.zeros(0, np.uint8))
         for n_layers in (1, 2):
             assert np.array_equal(_run(pack.bytes(), rec, tables, S, n_layers=n_layers), want), (shift, n_layers)
@@ -185,9 +182,8 @@ def test_mix_tracks_the_reference_mixup_within_one_step():
             for l in range(2):
                 im = rs.randint(0, 256, size=(S, S, 3)).astype(np.uint8)
                 lay = rec[b]["layer"][l]
-                lay["m"], lay["n_tiles"] = A.IDENTITY, 1
-                t = lay["tile"][0]
-                t["src_offset"], t["h"], t["w"], t["x1"], t["y1"] = pack.add(im), S, S, S, S
+                fill_single_layer(lay, A.IDENTITY, S, S, 0, 0)
+                lay["tile"][0]["src_offset"] = pack.add(im)
             want.append(g["mixed"])
         pack.add(np.zeros(0, np.uint8))
         got = _run(pack.bytes(), rec, None, S)

@@ -13,8 +13,8 @@ import pytest
 import _augref as A
 import _mosaicref as R
 from adaptiveisp_amd import _lib
-from adaptiveisp_amd.augment import (Hyp, draw, draw_mosaic, finish_labels, fixed_inverse, mix_q16, mosaic_boxes, mosaic_tiles,
-                                     warp_labels)
+from adaptiveisp_amd.augment import (Hyp, draw, draw_mosaic, fill_mosaic_layer, fill_single_layer, finish_labels, fixed_inverse,
+                                     mix_q16, mosaic_boxes, mosaic_tiles, warp_labels)
 from adaptiveisp_amd.data import ImageFolderSource
 from test_augment_host import _write_pngs
 
@@ -45,12 +45,11 @@ def records_of(g, m, fill=GREY, gap=0):
     rec = np.zeros(1, _lib.MOSAIC_DESC)
     rec["n_layers"], rec["lut"], rec["mix"] = 1, -1, 65536
     lay = rec[0]["layer"][0]
-    lay["m"], lay["fill"], lay["n_tiles"] = m, fill, 4
+    fill_mosaic_layer(lay, m, sizes, mosaic_tiles(sizes, tuple(int(v) for v in g["centre"]), S))
+    lay["fill"] = fill
     chunks, off = [], 0
-    for k, (i, row) in enumerate(zip(order, mosaic_tiles(sizes, tuple(int(v) for v in g["centre"]), S))):
-        t = lay["tile"][k]
-        t["src_offset"], t["h"], t["w"] = off + gap, sizes[k][0], sizes[k][1]
-        t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = row
+    for k, i in enumerate(order):
+        lay["tile"][k]["src_offset"] = off + gap
         chunks += [np.full(gap, 77, np.uint8), g["tiles"][i].reshape(-1)]
         off += gap + g["tiles"][i].size
     return rec, np.concatenate(chunks)
@@ -134,9 +133,8 @@ def test_restatement_one_layer_one_tile_is_the_augment_restatement():
     rec = np.zeros(1, _lib.MOSAIC_DESC)
     rec["n_layers"], rec["lut"] = 1, 0
     lay = rec[0]["layer"][0]
-    lay["m"], lay["fill"], lay["n_tiles"] = m, 0x302010, 1
-    t = lay["tile"][0]
-    t["src_offset"], t["h"], t["w"], t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = 5, 31, 44, 3, 9, 47, 40, 3, 9
+    fill_single_layer(lay, m, 31, 44, 9, 3)
+    lay["fill"], lay["tile"][0]["src_offset"] = 0x302010, 5
     src = np.concatenate([np.full(5, 9, np.uint8), img.reshape(-1)])
     luts = d.luts.reshape(1, 768)
     assert np.array_equal(R.mosaic(src, rec[0], S, luts), A.augment(img, 9, 3, m.tolist(), S, 0x302010, luts[0]))
@@ -344,3 +342,39 @@ def test_header_exports_and_descriptor_layout():
     src = open(os.path.join(ROOT, "adaptiveisp_amd", "csrc", "isp_augment.hip")).read()
     m = re.search(r"sizeof\(adaisp_mosaic_tile\) == (\d+) && sizeof\(adaisp_mosaic_layer\) == (\d+) && sizeof\(adaisp_mosaic_desc\) == (\d+)", src)
     assert m and [int(v) for v in m.groups()] == [40, 216, 448]
+
+
+def test_record_helpers_fill_what_a_hand_filled_record_holds():
+    """augment.fill_mosaic_layer / fill_single_layer against records filled field by field from mosaic_tiles."""
+    S, rng, rs = 64, random.Random(11), np.random.RandomState(11)
+    hyp = Hyp(degrees=10, shear=5, flipud=0.5)
+    mz = draw_mosaic(hyp, rng, rs, S, 9, 4)
+    sizes = [(64, 40), (33, 64), (64, 64), (17, 29)]
+    tiles = mosaic_tiles(sizes, mz.centre, S)
+    m = fixed_inverse(mz.M, True, False, S)
+    got, want = np.zeros(1, _lib.MOSAIC_DESC), np.zeros(1, _lib.MOSAIC_DESC)
+    fill_mosaic_layer(got[0]["layer"][1], m, sizes, tiles)
+    lay = want[0]["layer"][1]
+    lay["m"], lay["n_tiles"] = m, 4
+    for k in range(4):
+        t = lay["tile"][k]
+        t["h"], t["w"] = sizes[k]
+        t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = tiles[k]
+    assert got.tobytes() == want.tobytes() and all(np.array_equal(got[n], want[n]) for n in _lib.MOSAIC_DESC.names)
+    assert got[0]["layer"][1]["tile"]["x1"].tolist() == tiles[:, 2].tolist() and (got[0]["layer"][0]["n_tiles"], got[0]["mix"]) == (0, 0)
+    # a single letterboxed image: one tile over its own rectangle, moved by (left, top)
+    d = draw(hyp, rng, rs, S)
+    m, (h, w, top, left) = fixed_inverse(d.M, d.flipud, d.fliplr, S), (31, 44, 9, 3)
+    got, want = np.zeros(1, _lib.MOSAIC_DESC), np.zeros(1, _lib.MOSAIC_DESC)
+    for r in (got, want):
+        r["n_layers"], r["lut"], r["mix"] = 1, -1, _lib.MOSAIC_MIX_ONE
+    fill_single_layer(got[0]["layer"][0], m, h, w, top, left)
+    lay = want[0]["layer"][0]
+    lay["m"], lay["n_tiles"] = m, 1
+    t = lay["tile"][0]
+    t["h"], t["w"], t["dx"], t["dy"] = h, w, left, top
+    t["x0"], t["y0"], t["x1"], t["y1"] = left, top, left + w, top + h
+    assert got.tobytes() == want.tobytes() and got[0]["layer"][0]["tile"][0]["x1"] == 47 and got[0]["layer"][0]["tile"][0]["y1"] == 40
+    _lib._check_mosaic_records(got, h * w * 3, 0)
+    with pytest.raises(_lib.AdaispError, match="outside src"):
+        _lib._check_mosaic_records(got, h * w * 3 - 1, 0)

@@ -6,9 +6,11 @@
   unprocess          adaisp_unprocess with noise on the 8 frames the first arm wrote, for scale
 The arms alternate in one process, `--rounds` rounds of `--reps` launches each between a pair of device events, after a
 discarded warm-up round; inputs rotate over `--bufs` staged batches. One JSON line: the median microseconds of each arm over
-the rounds, their spread, and the GB/s against the algorithmic bytes (augment: 3 B/px read + 3 written; unprocess: 3 + 12).
+the rounds, their spread, the GB/s against the algorithmic bytes (augment: 3 B/px read + 3 written; unprocess: 3 + 12), and the
+sha256 of the frames each augment arm writes from the first batch (taken once, outside the timed loops).
     python tools/augment_bench.py [--reps 200] [--rounds 7] [--bufs 4] [--out FILE]"""
 import argparse
+import hashlib
 import json
 import os
 import random
@@ -74,6 +76,10 @@ def main():
         return e0.elapsed_time(e1) / a.reps * 1e3
 
     keys = ["augment", "augment_no_tables", "augment_identity", "unprocess"]      # unprocess last: it reads the first arm's frames
+    sha = {}
+    for k in keys[:3]:                                          # each arm's frames from the first batch, outside the timed loops
+        run(k)(0)
+        sha[k] = hashlib.sha256(frames.cpu().numpy().tobytes()).hexdigest()
     t = {k: [] for k in keys}
     for r in range(a.rounds + 1):                               # round 0 is the warm-up
         for k in keys[:1] + keys[3:] + keys[1:3]:
@@ -87,6 +93,8 @@ def main():
         line[k + "_us"] = round(med[k], 2)
         line[k + "_min_max_us"] = [round(min(t[k]), 2), round(max(t[k]), 2)]
         line[k + "_GBps"] = round((UNP_BYTES if k == "unprocess" else AUG_BYTES) * px / med[k] / 1e3, 1)
+        if k in sha:
+            line[k + "_sha256"] = sha[k]
     line["tables_us_by_difference"] = round(med["augment"] - med["augment_no_tables"], 2)
     line["gathers_us_by_difference"] = round(med["augment_no_tables"] - med["augment_identity"], 2)
     line["augment_over_unprocess"] = round(med["augment"] / med["unprocess"], 3)

@@ -8,9 +8,11 @@
   augment          adaisp_augment_u8 on the same images, maps and tables (the two write the same bytes; checked once)
 The arms alternate in one process, `--rounds` rounds of `--reps` launches each between a pair of device events, after a
 discarded warm-up round; inputs rotate over `--bufs` staged pools. One JSON line: the median microseconds of each arm over
-the rounds, their spread, the ratios to `augment`, and the source bytes a batch of each kind stages.
+the rounds, their spread, the ratios to `augment`, the source bytes a batch of each kind stages, and the sha256 of the frames
+each arm writes from the first pool (taken once, outside the timed loops: two builds of the kernel compare by it).
     python tools/mosaic_bench.py [--reps 200] [--rounds 7] [--bufs 2] [--out FILE]"""
 import argparse
+import hashlib
 import json
 import os
 import random
@@ -32,7 +34,8 @@ def main():
     import torch
     sys.path.insert(0, ROOT)
     from adaptiveisp_amd import _lib
-    from adaptiveisp_amd.augment import Hyp, draw, draw_mosaic, fixed_inverse, mix_q16, mosaic_tiles
+    from adaptiveisp_amd.augment import (Hyp, draw, draw_mosaic, fill_mosaic_layer, fill_single_layer, fixed_inverse, mix_q16,
+                                         mosaic_tiles)
     if not torch.cuda.is_available():
         raise SystemExit("tools/mosaic_bench.py measures on the HIP device; there is none")
     rs, rng = np.random.RandomState(0), random.Random(0)
@@ -50,12 +53,9 @@ def main():
                 rec[b]["mix"] = mix_q16(rs.beta(32.0, 32.0))
             for l in range(layers):
                 mz = draw_mosaic(hyp, rng, rs, S, POOL, (8 * l + b) % POOL)
-                lay = rec[b]["layer"][l]
-                lay["m"], lay["n_tiles"] = fixed_inverse(mz.M, d.flipud, d.fliplr, S), 4
-                for k, row in enumerate(mosaic_tiles([(S, S)] * 4, mz.centre, S)):
-                    t = lay["tile"][k]
-                    t["src_offset"], t["h"], t["w"] = mz.indices[k] * image, S, S
-                    t["x0"], t["y0"], t["x1"], t["y1"], t["dx"], t["dy"] = row
+                lay, sizes = rec[b]["layer"][l], [(S, S)] * 4
+                fill_mosaic_layer(lay, fixed_inverse(mz.M, d.flipud, d.fliplr, S), sizes, mosaic_tiles(sizes, mz.centre, S))
+                lay["tile"]["src_offset"] = np.array(mz.indices) * image
         return rec
 
     one = np.zeros(B, _lib.MOSAIC_DESC)
@@ -64,10 +64,8 @@ def main():
     for b, d in enumerate(draws):
         m = fixed_inverse(d.M, d.flipud, d.fliplr, S)
         aug[b]["src_offset"], aug[b]["h"], aug[b]["w"], aug[b]["m"], aug[b]["lut"] = b * image, S, S, m, b
-        lay = one[b]["layer"][0]
-        lay["m"], lay["n_tiles"], one[b]["lut"] = m, 1, b
-        t = lay["tile"][0]
-        t["src_offset"], t["h"], t["w"], t["x1"], t["y1"] = b * image, S, S, S, S
+        fill_single_layer(one[b]["layer"][0], m, S, S, 0, 0)
+        one[b]["lut"], one[b]["layer"][0]["tile"][0]["src_offset"] = b, b * image
     host = {"mosaic_four": mosaic_records(1), "mosaic_mixup": mosaic_records(2), "mosaic_one_tile": one, "augment": aug}
     dev = {k: torch.from_numpy(v.view(np.uint8).copy()).cuda() for k, v in host.items()}
     srcs = [torch.from_numpy(rs.randint(0, 256, POOL * image).astype(np.uint8)).cuda() for _ in range(a.bufs)]
@@ -94,6 +92,10 @@ def main():
         return e0.elapsed_time(e1) / a.reps * 1e3
 
     keys = list(host)
+    sha = {}
+    for k in keys:                                              # each arm's frames from the first pool, outside the timed loops
+        run(k)(0)
+        sha[k] = hashlib.sha256(frames.cpu().numpy().tobytes()).hexdigest()
     t = {k: [] for k in keys}
     for r in range(a.rounds + 1):                               # round 0 is the warm-up
         for k in keys[r % len(keys):] + keys[:r % len(keys)]:   # the order rotates from round to round
@@ -107,6 +109,7 @@ def main():
         line[k + "_us"] = round(med[k], 2)
         line[k + "_min_max_us"] = [round(min(t[k]), 2), round(max(t[k]), 2)]
         line[k + "_over_augment"] = round(med[k] / med["augment"], 3)
+        line[k + "_sha256"] = sha[k]
     line["record_bytes"] = dict(mosaic=_lib.MOSAIC_DESC.itemsize, augment=_lib.AUGMENT_DESC.itemsize)
     line["staged_source_MB_per_batch"] = dict(augment=round(B * image / 1e6, 1), mosaic_four=round(4 * B * image / 1e6, 1),
                                               mosaic_mixup=round(8 * B * image / 1e6, 1))
