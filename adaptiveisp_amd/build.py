@@ -20,7 +20,7 @@ LIBS = {
         headers=["isp_internal.h", "isp_filter_math.h", "isp_unprocess_math.h", "isp_policy_math.h", "isp_demosaic_math.h", "isp_csr.h", "../../include/adaisp.h"],
         flags=ISP_FLAGS),
     "libadayolo.so": dict(
-        sources=["yolo_conv_dma.hip", "yolo_conv_dma2.hip", "yolo_conv_small.hip", "yolo_conv_pp.hip", "yolo_conv_chain.hip", "yolo_bneck.hip", "yolo_bneck_ws.hip", "yolo_conv_pp128.hip", "yolo_conv_k1.hip", "yolo_conv_pq.hip", "yolo_conv_ws.hip", "yolo_misc.hip", "yolo_stem_down.hip", "yolo_nms.hip", "yolo_nms_batch.hip", "yolo_match.hip", "yolo_train.hip", "yolo_loss.hip", "yolo_api.hip"],
+        sources=["yolo_conv_dma.hip", "yolo_conv_dma2.hip", "yolo_conv_small.hip", "yolo_conv_pp.hip", "yolo_conv_chain.hip", "yolo_bneck.hip", "yolo_bneck_ws.hip", "yolo_conv_pp128.hip", "yolo_conv_k1.hip", "yolo_conv_pq.hip", "yolo_conv_ws.hip", "yolo_misc.hip", "yolo_spp.hip", "yolo_stem_down.hip", "yolo_nms.hip", "yolo_nms_batch.hip", "yolo_match.hip", "yolo_train.hip", "yolo_loss.hip", "yolo_api.hip"],
         headers=["yolo_internal.h", "yolo_device.h", "yolo_chain.h", "yolo_nms_iou.h", "yolo_ring.h", "yolo_tile_pp.h", "yolo_tile_pp128.h", "../../include/adayolo.h"],
         flags=["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + os.environ.get("ADAYOLO_EXTRA_FLAGS", "").split()),
 }

@@ -676,6 +676,30 @@ int adayolo_upsample2x_bwd(const void* grad_out, int go_cstride, void* grad_in, 
                                     static_cast<hipStream_t>(stream)));
 }
 
+// a [B,H,W,cs] tensor whose every element offset fits 31 bits
+static bool fits31(int B, int H, int W, int cs) {
+    long n = (long)B * H;                                     // (each product of two values below 2^31 fits a long)
+    if (n > 0x7fffffffL || (n *= W) > 0x7fffffffL) return false;
+    return n * cs <= 0x7fffffffL;
+}
+
+int adayolo_spp_fwd(const void* x, int x_cstride, void* out, int out_cstride, int B, int H, int W, int C, void* stream) {
+    if (!x || !out) return ADAYOLO_EINVAL;
+    if (B < 1 || H < 1 || W < 1 || !ok8(C, x_cstride) || out_cstride % 8 || out_cstride < 3L * C) return ADAYOLO_ESHAPE;
+    if (!fits31(B, H, W, x_cstride) || !fits31(B, H, W, out_cstride)) return ADAYOLO_ESHAPE;
+    return code(launch_spp_fwd(x, x_cstride, out, out_cstride, B, H, W, C, static_cast<hipStream_t>(stream)), ADAYOLO_ESHAPE);
+}
+
+int adayolo_spp_bwd(const void* x, int x_cstride, const void* grad_out, int go_cstride, void* grad_x, int gx_cstride,
+                    int accumulate, int B, int H, int W, int C, void* stream) {
+    if (!x || !grad_out || !grad_x) return ADAYOLO_EINVAL;
+    if (B < 1 || H < 1 || W < 1 || !ok8(C, x_cstride) || !ok8(C, gx_cstride) || go_cstride % 8 || go_cstride < 3L * C)
+        return ADAYOLO_ESHAPE;
+    if (!fits31(B, H, W, x_cstride) || !fits31(B, H, W, go_cstride) || !fits31(B, H, W, gx_cstride)) return ADAYOLO_ESHAPE;
+    return code(launch_spp_bwd(x, x_cstride, grad_out, go_cstride, grad_x, gx_cstride, accumulate, B, H, W, C,
+                               static_cast<hipStream_t>(stream)), ADAYOLO_ESHAPE);
+}
+
 int adayolo_image_grad(const void* grad_nhwc, int g_cstride, float* grad_img, int B, int H, int W, int Hp, int pad_top,
                        void* stream) {
     if (!grad_nhwc || !grad_img || bad_frame(B, H, W, Hp, pad_top)) return ADAYOLO_EINVAL;

@@ -124,6 +124,10 @@ hipError_t launch_zero_insert(const void* in, int in_cs, void* out, int out_cs, 
                               hipStream_t s);
 hipError_t launch_upsample_bwd(const void* gy, int gy_cs, void* gx, int gx_cs, int accumulate, int B, int H, int W, int C,
                                hipStream_t s);
+// SPP's three max pools (5, 9, 13; stride 1) in one launch and their gradient in one (yolo_spp.hip)
+hipError_t launch_spp_fwd(const void* x, int x_cs, void* out, int out_cs, int B, int H, int W, int C, hipStream_t s);
+hipError_t launch_spp_bwd(const void* x, int x_cs, const void* gout, int go_cs, void* gx, int gx_cs, int accumulate, int B, int H,
+                          int W, int C, hipStream_t s);
 hipError_t launch_image_grad(const void* g, int g_cs, float* grad_img, int B, int H, int W, int Hp, int pad_top,
                              hipStream_t s);
 hipError_t launch_detloss_fwd(const adayolo_loss_args& a, hipStream_t s);   // yolo_loss.hip

@@ -383,7 +383,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
                   detector_ckpt=None, isp_ckpt=None, source=None, seed=0, tune_cache=None, data=None, data_name="lod",
                   add_noise=False, brightness_range=None, noise_level=None, use_linear=False, workers=4, resize="host",
                   sensor="rgb", cfa="RGGB", raw_bits=12, black_level=None, demosaic="bilinear", raw_gains=(1.0, 1.0, 1.0),
-                  raw_calibration=None, raw_meta=False, augment=None, mosaic=0.0, mixup=0.0):
+                  raw_calibration=None, raw_meta=False, augment=None, mosaic=0.0, mixup=0.0, detector_cfg="yolov3"):
     """Everything one rank owns: its own replay pool in HBM (seeded by rank, so ranks draw different records), the
     frozen detector on the HIP training engine, agent / value / optimizers. Rank 0's weights are broadcast.
     `data`: a directory or .txt list of images fed through data.ImageFolderSource (`data_name` "lod" or "coco", with the
@@ -393,13 +393,14 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
     `black_level` sensor and its `demosaic`, "bilinear" or "mhc"; `augment`: None, or the hyper-parameters (an augment.Hyp, a
     dict or a YAML path) of the affine warp / HSV / flip augmentation, one HIP launch per batch; `mosaic`, `mixup`: with
     `augment`, the probabilities of a four-image mosaic and of blending it with a second one, in that same launch); None:
-    SyntheticSource."""
+    SyntheticSource. `detector_cfg`: "yolov3" or "yolov3-spp", the graph of the randomly initialised detector when there is no
+    `detector_ckpt` (a checkpoint brings its own)."""
     import random
 
     from .agent import Agent
     from .replay import DeviceReplayMemory, SyntheticSource
     from .value import Value
-    from .yolo import YoloTrainEngine, YoloTrainPairEngine, yolov3
+    from .yolo import DetectionModel, YoloTrainEngine, YoloTrainPairEngine
     from .yolo.checkpoint import load_detector_checkpoint, load_isp_checkpoint
     from .yolo.loss import DetectionLoss, default_hyp
     H = W = int(image_size)
@@ -408,7 +409,7 @@ def build_trainer(cfg, rank, world, device, batch_size, image_size, lr=3e-5, epo
     value = Value(cfg, shape=(9 + len(cfg.filters), 64, 64)).to(device)
     if isp_ckpt:
         load_isp_checkpoint(isp_ckpt, agent, value, map_location=device)
-    det = load_detector_checkpoint(detector_ckpt) if detector_ckpt else yolov3()
+    det = load_detector_checkpoint(detector_ckpt) if detector_ckpt else DetectionModel(cfg=detector_cfg)
     det = det.to(device).train()
     for m in det.modules():                                   # frozen reward model (train.py:236-243)
         if isinstance(m, torch.nn.BatchNorm2d):
@@ -450,7 +451,10 @@ def build_parser():
     ap.add_argument("--epochs", type=int, default=800)
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--sync-bn", action="store_true")
-    ap.add_argument("--detector-ckpt", default=None, help="yolov3.pt (pickled reference module)")
+    ap.add_argument("--detector-ckpt", default=None, help="yolov3.pt or yolov3-spp.pt (pickled reference module)")
+    ap.add_argument("--detector-cfg", default=None, choices=("yolov3", "yolov3-spp"),
+                    help="graph of the randomly initialised detector when there is no --detector-ckpt (default: yolov3); a "
+                         "checkpoint brings its own graph, and naming the other one is an error")
     ap.add_argument("--isp-ckpt", default=None, help="ckpt-*.pth to resume from")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--data", default=None, help="image directory or .txt list to train on (default: synthetic images)")
@@ -508,6 +512,11 @@ def parse_args(argv=None):
         ap.error("--data-name raw with --sensor bayer: the planes already are a sensor's")
     if a.data_name != "raw" and (a.raw_cal is not None or a.raw_dpc is not None or a.raw_meta):
         ap.error("--raw-cal / --raw-dpc / --raw-meta need --data-name raw")
+    try:
+        from .yolo.checkpoint import resolve_detector_cfg
+        a.detector_cfg = resolve_detector_cfg(a.detector_ckpt, a.detector_cfg)
+    except ValueError as e:
+        ap.error(str(e))
     a.augment = a.augment or a.hyp is not None
     if a.augment and a.data is None:
         ap.error("--augment / --hyp need --data (the synthetic source is not augmented)")
@@ -578,7 +587,7 @@ def main(argv=None):
                            raw_gains=tuple(a.raw_gains),
                            raw_calibration=calibration_from_options(a.raw_cal, a.raw_dpc, a.cfa), raw_meta=a.raw_meta,
                            augment=(a.hyp if a.hyp is not None else {}) if a.augment else None, mosaic=a.mosaic,
-                           mixup=a.mixup)
+                           mixup=a.mixup, detector_cfg=a.detector_cfg or "yolov3")
     n = tr.max_iter_step + 1 if a.iters is None else a.iters
     tr.train(min(a.warmup, n))
 

@@ -77,7 +77,11 @@ def build_parser():
     ap = argparse.ArgumentParser(prog="python -m adaptiveisp_amd.val",
                                  description="Evaluate an ISP policy checkpoint with a YOLOv3 detector (mAP, records, outputs)")
     ap.add_argument("--isp-ckpt", required=True, help="ISP checkpoint (ckpt-*.pth; its 'agent_model' is loaded)")
-    ap.add_argument("--detector-ckpt", default=None, help="yolov3.pt (default: a random-init YOLOv3, for smoke runs only)")
+    ap.add_argument("--detector-ckpt", default=None,
+                    help="yolov3.pt or yolov3-spp.pt (default: a random-init detector, for smoke runs only)")
+    ap.add_argument("--detector-cfg", default=None, choices=("yolov3", "yolov3-spp"),
+                    help="graph of the random-init detector when there is no --detector-ckpt (default: yolov3); a checkpoint "
+                         "brings its own graph, and naming the other one is an error")
     ap.add_argument("--data", required=True, help="dataset YAML, or an image directory / .txt list / image")
     ap.add_argument("--task", default="val", choices=("val", "test", "train"), help="which YAML entry to evaluate")
     ap.add_argument("--data-name", default="lod", choices=("lod", "coco", "raw"),
@@ -147,6 +151,11 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.batch_size < 1 or a.steps < 1:
         ap.error("--batch-size and --steps must be positive")
+    try:
+        from ..yolo.checkpoint import resolve_detector_cfg
+        a.detector_cfg = resolve_detector_cfg(a.detector_ckpt, a.detector_cfg)
+    except ValueError as e:
+        ap.error(str(e))
     if a.nms == "device" and a.match != "device":
         # the device NMS leaves its rows where adayolo_match reads them: there is no host matching behind it
         print("--nms device: matching runs on the device too (--match device)")
@@ -221,7 +230,7 @@ def main(argv=None):
     from ..config import cfg
     from ..data import ImageFolderSource
     from ..rawcal import calibration_from_options
-    from ..yolo import YoloEngine, yolov3
+    from ..yolo import DetectionModel, YoloEngine
     from ..yolo.checkpoint import load_detector_checkpoint, load_isp_checkpoint
     from . import writers
     from .harness import run_eval
@@ -238,8 +247,8 @@ def main(argv=None):
         names = det.names if isinstance(det.names, dict) else dict(enumerate(det.names))
         ckpt_nc = len(names)
     else:
-        print("WARNING: no --detector-ckpt: a randomly initialised YOLOv3 (the numbers mean nothing; smoke runs only)")
-        det = yolov3(nc=yaml_nc or 80)
+        print(f"WARNING: no --detector-ckpt: a randomly initialised {a.detector_cfg} (the numbers mean nothing; smoke runs only)")
+        det = DetectionModel(cfg=a.detector_cfg, nc=yaml_nc or 80)
         names, ckpt_nc = None, None
     if yaml_nc is not None and ckpt_nc is not None and yaml_nc != ckpt_nc and not a.single_cls:
         raise SystemExit(f"{a.detector_ckpt} ({ckpt_nc} classes) was trained on different data than --data {a.data} "

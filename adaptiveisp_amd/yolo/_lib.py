@@ -11,6 +11,7 @@ ABI_VERSION = 10
 ACT_NONE, ACT_SILU = 0, 1
 EXPORTS = ("adayolo_conv_fwd", "adayolo_conv_fwd_variant", "adayolo_conv_fused1x1_fwd", "adayolo_conv1x1_stream_fwd", "adayolo_bottleneck256_fwd", "adayolo_bottleneck_ws_fwd", "adayolo_conv_keep_fwd", "adayolo_conv_splitk_fwd", "adayolo_conv_dsilu_fwd", "adayolo_conv_s2grad_fwd", "adayolo_conv_splitk_workspace_bytes", "adayolo_conv_chain_workspace_bytes", "adayolo_conv_chain_prepare", "adayolo_conv_chain_fwd", "adayolo_conv_chain_status", "adayolo_conv_chain_poll", "adayolo_conv_chain_tables", "adayolo_stem_fwd", "adayolo_upsample2x", "adayolo_detect_decode", "adayolo_nms", "adayolo_nms_workspace_bytes", "adayolo_match", "adayolo_nms_batch", "adayolo_nms_batch_workspace_bytes", "adayolo_stem_fwd_act", "adayolo_stem_keep_fwd", "adayolo_stem_down_fwd", "adayolo_letterbox_pack", "adayolo_silu_fwd", "adayolo_silu_bwd",
            "adayolo_zero_insert2x", "adayolo_upsample2x_bwd", "adayolo_image_grad", "adayolo_detloss_fwd", "adayolo_detloss_bwd",
+           "adayolo_spp_fwd", "adayolo_spp_bwd",
            "adayolo_strerror", "adayolo_set_mfma_shape", "adayolo_get_mfma_shape",
            "adayolo_abi_version")
 _lib = None
@@ -104,8 +105,10 @@ def load(path=None):
     L.adayolo_zero_insert2x.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp]
     L.adayolo_upsample2x_bwd.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]
     L.adayolo_image_grad.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, vp]
+    L.adayolo_spp_fwd.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, vp]
+    L.adayolo_spp_bwd.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]
     for n in ("adayolo_stem_fwd_act", "adayolo_stem_keep_fwd", "adayolo_stem_down_fwd", "adayolo_letterbox_pack", "adayolo_silu_fwd", "adayolo_silu_bwd", "adayolo_zero_insert2x",
-              "adayolo_upsample2x_bwd", "adayolo_image_grad"):
+              "adayolo_upsample2x_bwd", "adayolo_image_grad", "adayolo_spp_fwd", "adayolo_spp_bwd"):
         getattr(L, n).restype = ci
     for n in ("adayolo_detloss_fwd", "adayolo_detloss_bwd"):
         getattr(L, n).argtypes = [ctypes.POINTER(LossArgs), vp]

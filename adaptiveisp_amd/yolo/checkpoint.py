@@ -163,9 +163,32 @@ def read_detector_pickle(path):
                 source=src, epoch=ckpt.get("epoch") if isinstance(ckpt.get("epoch"), int) else None)
 
 
+def _graph_of(sd):
+    """The graph is in the keys: layer 12 is SPP (cv1 / cv2; a conv bias after fuse(), which _defuse turned back into a BN) in
+    yolov3-spp.yaml, one Conv in yolov3.yaml."""
+    return "yolov3-spp" if "model.12.cv1.conv.weight" in sd or "model.12.cv1.conv.bias" in sd else "yolov3"
+
+
+def resolve_detector_cfg(ckpt, cfg):
+    """The graph name a command line's --detector-ckpt / --detector-cfg pair means. Without a checkpoint: `cfg`, else
+    "yolov3". With one the graph comes from the file: None when `cfg` is None (the file is not opened here), and a `cfg`
+    that names the other graph is a ValueError naming both."""
+    from .model import graph_name
+    want = graph_name(cfg) if cfg is not None else None
+    if not ckpt:
+        return want or "yolov3"
+    if want is None:
+        return None
+    have = _graph_of(read_detector_pickle(ckpt)["state_dict"])
+    if want != have:
+        raise ValueError(f"--detector-cfg {want} contradicts --detector-ckpt {ckpt}, which holds a {have} graph")
+    return have
+
+
 def load_detector_checkpoint(path, width=None):
-    """yolov3.pt -> DetectionModel in eval mode with the checkpoint's weights (fp32). `width`: channel multiple of
-    the pickled model (1.0 for the released yolov3.pt; inferred from the widest conv when None)."""
+    """yolov3.pt / yolov3-spp.pt -> DetectionModel in eval mode with the checkpoint's weights (fp32); which of the two graphs
+    is read from the keys. `width`: channel multiple of the pickled model (1.0 for the released files; inferred from the
+    widest conv when None)."""
     info = read_detector_pickle(path)
     sd = info["state_dict"]
     if width is None:
@@ -174,12 +197,13 @@ def load_detector_checkpoint(path, width=None):
     anchors = None
     if info["anchors"] is not None:
         anchors = tuple(tuple(float(v) for v in a.reshape(-1)) for a in info["anchors"])
-    model = DetectionModel(nc=nc, anchors=anchors, width=width)
+    cfg = _graph_of(sd)
+    model = DetectionModel(cfg=cfg, nc=nc, anchors=anchors, width=width)
     missing, unexpected = model.load_state_dict(sd, strict=False)
     unexpected = [k for k in unexpected if not k.endswith("anchor_grid")]
     if missing or unexpected:
-        raise ValueError(f"{path}: state dict does not match the YOLOv3 layout (missing {missing[:4]}, "
-                         f"unexpected {unexpected[:4]})")
+        raise ValueError(f"{path}: state dict does not match the YOLOv3 layout (model.12.conv.*) nor the YOLOv3-SPP layout "
+                         f"(model.12.cv1.* / model.12.cv2.*): read as {cfg}, missing {missing[:4]}, unexpected {unexpected[:4]}")
     if info["names"]:
         model.names = info["names"]
     return model.eval()

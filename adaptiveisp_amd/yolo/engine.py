@@ -10,6 +10,8 @@ bias + SiLU + residual epilogue:
     Conv(3->32)+SiLU in one kernel — no separate pad / layout / dtype pass;
   * Concat is free: the two producers write straight into channel slices of the concatenated tensor
     (the convs take channel strides), Upsample is a scatter into its slice;
+  * SPP (yolov3-spp): cv1 writes channel slice 0 of a 4C tensor, ONE launch writes its 5 / 9 / 13 max pools into slices 1..3
+    (adayolo_spp_fwd), cv2 is an ordinary 1x1 conv over the 4C channels;
   * Detect: 1x1 conv to 255(+1 pad) channels, then one decode kernel writes the [B, N, 85] fp32 prediction.
 
 There is no eager fallback: without libadayolo.so / a HIP device this raises.
@@ -21,7 +23,7 @@ import os
 import torch
 
 from . import _lib
-from .model import Bottleneck, Concat, Conv, Detect, DetectionModel
+from .model import SPP, Bottleneck, Concat, Conv, Detect, DetectionModel
 
 LETTERBOX_VALUE = 114.0 / 255.0     # yolov3/utils/augmentations.py:111 (color=(114,114,114)) on a [0,1] image
 
@@ -241,6 +243,8 @@ class YoloEngine:
             elif isinstance(m, (Bottleneck, torch.nn.Sequential)):
                 last = m if isinstance(m, Bottleneck) else m[-1]
                 shp.append((last.cv2.conv.out_channels, prev[1], prev[2]))
+            elif isinstance(m, SPP):
+                shp.append((m.cv2.conv.out_channels, prev[1], prev[2]))
             elif isinstance(m, torch.nn.Upsample):
                 shp.append((prev[0], prev[1] * 2, prev[2] * 2))
             elif isinstance(m, Concat):
@@ -264,6 +268,8 @@ class YoloEngine:
             if view[i] is None and shp[i] is not None:
                 C, H, W = shp[i]
                 view[i] = _View(self._new(H, W, C), 0, C)
+        # SPP's own concat [cv1(x), mp5, mp9, mp13]: one 4C tensor per SPP layer
+        spp_cat = {i: self._new(shp[i][1], shp[i][2], 4 * m.cv1.conv.out_channels) for i, m in enumerate(layers) if isinstance(m, SPP)}
         # pass 3: launch plan
         for i, m in enumerate(layers):
             src = view[_src(i, m.f)] if (i > 0 and isinstance(m.f, int)) else None
@@ -309,6 +315,16 @@ class YoloEngine:
                     self._conv_op(cur, w1, b1, hidden, 1, 1, _lib.ACT_SILU)
                     self._conv_op(hidden, w2, b2, out, 3, 1, _lib.ACT_SILU, res=cur if blk.add else None)
                     cur = out
+            elif isinstance(m, SPP):
+                c_ = m.cv1.conv.out_channels
+                if c_ % 8 or [p.kernel_size for p in m.m] != [5, 9, 13] or any(p.stride != 1 or p.padding != p.kernel_size // 2 for p in m.m):
+                    raise _lib.AdayoloError("SPP: adayolo_spp_fwd serves pools (5, 9, 13), stride 1, padding k // 2, on a multiple of 8 channels")
+                x, pools, cat = _View(spp_cat[i], 0, c_), _View(spp_cat[i], c_, 3 * c_), _View(spp_cat[i], 0, 4 * c_)
+                self._conv_op(src, *_pack_conv(*m.cv1.folded()), x, 1, 1, _lib.ACT_SILU)
+                args = (ctypes.c_void_p(x.ptr), x.cs, ctypes.c_void_p(pools.ptr), pools.cs, self.B, x.H, x.W, c_)
+                self.plan.append(("spp", self.L.adayolo_spp_fwd, args))
+                self.ops.append(dict(kind="spp", src=x, dst=pools))
+                self._conv_op(cat, *_pack_conv(*m.cv2.folded()), view[i], 1, 1, _lib.ACT_SILU)
             elif isinstance(m, torch.nn.Upsample):
                 args = (ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(view[i].ptr), view[i].cs, self.B, src.H,
                         src.W, src.C)

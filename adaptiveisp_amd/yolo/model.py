@@ -1,4 +1,4 @@
-"""YOLOv3 (Darknet-53 backbone, 3-scale head) as a plain parameter tree.
+"""YOLOv3 and YOLOv3-SPP (Darknet-53 backbone, 3-scale head) as a plain parameter tree.
 
 The module classes and their nesting reproduce the state-dict layout of the reference's detector
 (`model.N.conv.weight`, `model.N.bn.*`, `model.N.cv1/cv2.*`, `model.N.K.cv1.*` for repeated blocks,
@@ -28,6 +28,19 @@ GRAPH = (
     (-1, 1, "bneck", (256, False)), (-1, 2, "bneck", (256, False)),
     ((27, 22, 15), 1, "detect", ()),
 )
+# yolov3-spp.yaml: the same graph with layer 12 = SPP(512, (5, 9, 13)) in place of Conv(1024 -> 512, 1x1). SPP args: (cout, k)
+GRAPH_SPP = GRAPH[:12] + ((-1, 1, "spp", (512, (5, 9, 13))),) + GRAPH[13:]
+GRAPHS = {"yolov3": GRAPH, "yolov3-spp": GRAPH_SPP}
+
+
+def graph_name(cfg):
+    """"yolov3" / "yolov3-spp" for a cfg name, with or without .yaml and directories (the reference passes a yaml path)."""
+    import os
+    name = os.path.basename(str(cfg))
+    name = name[:-len(".yaml")] if name.endswith(".yaml") else name
+    if name not in GRAPHS:
+        raise ValueError(f"unknown detector cfg {cfg!r}: this package builds {' and '.join(sorted(GRAPHS))}")
+    return name
 
 
 class Conv(nn.Module):
@@ -59,6 +72,22 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         y = self.cv2(self.cv1(x))
         return x + y if self.add else y
+
+
+class SPP(nn.Module):
+    """Spatial pyramid pooling (yolov3/models/common.py:202-215): cv1 halves the channels, the map and its 5 / 9 / 13 max pools
+    (stride 1, padding k // 2) are concatenated, cv2 mixes the 4 * c_ channels."""
+
+    def __init__(self, c1, c2, k=(5, 9, 13)):
+        super().__init__()
+        c_ = c1 // 2
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_ * (len(k) + 1), c2, 1, 1)
+        self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])
+
+    def forward(self, x):
+        x = self.cv1(x)
+        return self.cv2(torch.cat([x] + [m(x) for m in self.m], 1))
 
 
 class Concat(nn.Module):
@@ -106,11 +135,13 @@ def make_divisible(x, divisor=8):
 class DetectionModel(nn.Module):
     def __init__(self, cfg="yolov3.yaml", ch=3, nc=80, anchors=None, width=1.0):
         """`width`: the yaml's width_multiple (1.0 = yolov3.yaml); channels are make_divisible(c * width, 8)
-        exactly as the reference's parse_model does (yolov3/models/yolo.py:299-356)."""
+        exactly as the reference's parse_model does (yolov3/models/yolo.py:299-356). `cfg`: "yolov3" or "yolov3-spp", also
+        as "<name>.yaml" or a path to one (only the name counts: the two graphs are built in)."""
         super().__init__()
+        self.cfg = graph_name(cfg)
         layers, chans = [], []
-        for frm, n, kind, args in GRAPH:
-            if kind in ("conv", "bneck") and width != 1.0:
+        for frm, n, kind, args in GRAPHS[self.cfg]:
+            if kind in ("conv", "bneck", "spp") and width != 1.0:
                 args = (make_divisible(args[0] * width, 8),) + tuple(args[1:])
             i = len(layers)
             c_prev = ch if i == 0 else (chans[i + frm if frm < 0 else frm] if isinstance(frm, int) else None)
@@ -119,6 +150,8 @@ class DetectionModel(nn.Module):
             elif kind == "bneck":
                 blocks = [Bottleneck(c_prev if j == 0 else args[0], args[0], args[1]) for j in range(n)]
                 m, c_out = (blocks[0] if n == 1 else nn.Sequential(*blocks)), args[0]
+            elif kind == "spp":
+                m, c_out = SPP(c_prev, args[0], args[1]), args[0]
             elif kind == "up":
                 m, c_out = nn.Upsample(None, 2, "nearest"), c_prev
             elif kind == "cat":
@@ -152,3 +185,7 @@ Model = DetectionModel
 
 def yolov3(nc=80):
     return DetectionModel(nc=nc)
+
+
+def yolov3_spp(nc=80):
+    return DetectionModel(cfg="yolov3-spp", nc=nc)

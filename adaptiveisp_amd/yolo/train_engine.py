@@ -10,7 +10,7 @@ Forward (train): every Conv keeps its pre-activation P (bf16): conv kernel witho
     dP = dY * silu'(P)  (adayolo_silu_bwd; the shortcut gradient is added into the block input's gradient there)
     dX (+)= conv(dP, W^T flipped)   — the SAME implicit-GEMM MFMA kernels as the forward (adayolo_conv_fwd_variant);
                                       stride-2 layers convolve the zero-inserted dP (adayolo_zero_insert2x)
-Upsample backward sums 2x2 blocks, Concat is free (gradients are read from channel slices), the stem's gradient is
+Upsample backward sums 2x2 blocks, SPP's three max pools route their gradient in one launch (adayolo_spp_bwd), Concat is free (gradients are read from channel slices), the stem's gradient is
 converted from NHWC bf16 to the planar fp32 image layout without the letterbox rows.
 Gradients are bf16 tensors (fp32 accumulation inside every kernel), like the activations.
 """
@@ -111,6 +111,11 @@ class YoloTrainEngine(YoloEngine):
                 self.tfwd.append(("up", L.adayolo_upsample2x, (ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(dst.ptr),
                                                                 dst.cs, B, src.H, src.W, src.C)))
                 bwd.append([("upbwd", L.adayolo_upsample2x_bwd, ("up", src, dst))])
+            elif op["kind"] == "spp":
+                src, dst = op["src"], op["dst"]                                       # slice 0 and slices 1..3 of SPP's 4C tensor
+                self.tfwd.append(("spp", L.adayolo_spp_fwd, (ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(dst.ptr), dst.cs,
+                                                              B, src.H, src.W, src.C)))
+                bwd.append([("sppbwd", L.adayolo_spp_bwd, (src, dst))])
             else:
                 src, dst, res, k, s, act, cout = (op[n] for n in ("src", "dst", "res", "k", "s", "act", "cout"))
                 w, b = op["w"], op["b"]
@@ -192,6 +197,16 @@ class YoloTrainEngine(YoloEngine):
                     self.tbwd.append(("upbwd", fn, (ctypes.c_void_p(gdst.ptr), gdst.cs, ctypes.c_void_p(gsrc.ptr), gsrc.cs,
                                                     int(is_written(gsrc)), self.B, src.H, src.W, src.C)))
                     meta.append(dict(reads=[gdst] + ([gsrc] if is_written(gsrc) else []), writes=[gsrc]))
+                    mark(gsrc)
+                elif kind == "sppbwd":
+                    # the pools' gradient (G of slices 1..3, routed to each window's first maximum of the kept activation) joins
+                    # the identity branch's, which cv2's data gradient has already left in G of slice 0
+                    src, dst = a
+                    gsrc, gdst = G(src), G(dst)
+                    acc = int(is_written(gsrc))
+                    self.tbwd.append(("sppbwd", fn, (ctypes.c_void_p(src.ptr), src.cs, ctypes.c_void_p(gdst.ptr), gdst.cs,
+                                                     ctypes.c_void_p(gsrc.ptr), gsrc.cs, acc, self.B, src.H, src.W, src.C)))
+                    meta.append(dict(reads=[gdst] + ([gsrc] if acc else []), writes=[gsrc]))
                     mark(gsrc)
                 elif kind == "dsilu":                                                   # the stem's
                     self.tbwd.append((kind, fn, a()))

@@ -318,6 +318,27 @@ int adayolo_upsample2x_bwd(const void* grad_out, int go_cstride, void* grad_in, 
 int adayolo_image_grad(const void* grad_nhwc, int g_cstride, float* grad_img, int B, int H, int W, int Hp, int pad_top,
                        void* stream);
 
+/*
+ * Spatial pyramid pooling (SPP(k = (5, 9, 13)), yolov3/models/common.py:202-215): the three stride-1 max pools of one map,
+ * padding k / 2, in one launch, and their gradient in one launch. NHWC bf16 with channel strides; any H and W.
+ *   adayolo_spp_fwd  reads x[B,H,W,C]; writes channels [0,C) of out = the 5x5 max, [C,2C) = 9x9, [2C,3C) = 13x13. Windows are
+ *                    clipped at the border (= MaxPool2d's -inf padding).
+ *   adayolo_spp_bwd  grad_x[p] (=|+=) sum over the three pools k and the pixels q with argmax_k(q) == p of grad_out_k[q]
+ *                    (grad_out's channel slices as above; accumulate != 0: +=). argmax_k(q) is the FIRST maximum of q's
+ *                    clipped window in row-major order (strict >; -0 == +0), recomputed from x. fp32 sums in a fixed order,
+ *                    rounded to bf16 once, no atomics: the same bits on every run. The identity branch of SPP's concat is
+ *                    the caller's (the engine has it in grad_x already and passes accumulate = 1).
+ * x and out (grad_out and grad_x) may be channel slices of ONE buffer — in the engine x is channels [0,C) and out channels
+ * [C,4C) of SPP's concatenated [B,H,W,4C] tensor: workgroups read their neighbours' x while others write out, so THE CALLER
+ * KEEPS THE TWO CHANNEL RANGES APART (no byte of x inside a written range of out, none of grad_out inside grad_x).
+ * ADAYOLO_EINVAL: a null pointer. ADAYOLO_ESHAPE: C < 8 or C % 8, a stride that is not a multiple of 8, x_cstride < C,
+ * out_cstride < 3C, go_cstride < 3C, gx_cstride < C, B, H or W < 1, a tensor beyond 31-bit element offsets.
+ * No allocation, no synchronisation: both can be captured into a graph.
+ */
+int adayolo_spp_fwd(const void* x, int x_cstride, void* out, int out_cstride, int B, int H, int W, int C, void* stream);
+int adayolo_spp_bwd(const void* x, int x_cstride, const void* grad_out, int go_cstride, void* grad_x, int gx_cstride,
+                    int accumulate, int B, int H, int W, int C, void* stream);
+
 /* Nearest 2x up-sampling of in[B,H,W,C] into a channel slice of out[B,2H,2W,*] (Upsample + Concat). */
 int adayolo_upsample2x(const void* in, int in_cstride, void* out, int out_cstride,
                        int B, int H, int W, int C, void* stream);

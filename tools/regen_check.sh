@@ -4,20 +4,23 @@
 #   tools/regen_check.sh            # all generators
 #   tools/regen_check.sh td,yolo    # some of them (`imggrad`: tests/golden/gen_imggrad.py, `unprocess`: tests/golden/gen_unprocess.py,
 #                                   # `valcli`: tests/golden/gen_valcli.py, `confusion`: tests/golden/gen_confusion.py,
-#                                   # `augment`: tests/golden/gen_augment.py, `mosaicaug`: tests/golden/gen_mosaic.py;
+#                                   # `augment`: tests/golden/gen_augment.py, `mosaicaug`: tests/golden/gen_mosaic.py,
+#                                   # `spp`: tests/golden/gen_spp.py — its two pickles are compared through the arrays of
+#                                   # ckpt_import_spp.npz, which are the outputs of the modules loaded back from them;
 #                                   # `mosaic` is gen_golden.py's Bayer fixture)
 set -e
 cd "$(dirname "$0")/.."
 OUT=$(mktemp -d /tmp/adaisp_regen.XXXXXX)
 cp tests/golden/state_dict_keys.json "$OUT"/ 2>/dev/null || true
 ARG=",${1:-},"
-NAMES=$(echo "$ARG" | sed 's/,imggrad,/,/; s/,unprocess,/,/; s/,valcli,/,/; s/,confusion,/,/; s/,augment,/,/; s/,mosaicaug,/,/; s/^,*//; s/,*$//')
+NAMES=$(echo "$ARG" | sed 's/,imggrad,/,/; s/,unprocess,/,/; s/,valcli,/,/; s/,confusion,/,/; s/,augment,/,/; s/,mosaicaug,/,/; s/,spp,/,/; s/^,*//; s/,*$//')
 if [ -z "${1:-}" ] || [[ "$ARG" == *,imggrad,* ]]; then python tests/golden/gen_imggrad.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,unprocess,* ]]; then python tests/golden/gen_unprocess.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,valcli,* ]]; then python tests/golden/gen_valcli.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,confusion,* ]]; then python tests/golden/gen_confusion.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,augment,* ]]; then python tests/golden/gen_augment.py --out "$OUT"; fi
 if [ -z "${1:-}" ] || [[ "$ARG" == *,mosaicaug,* ]]; then python tests/golden/gen_mosaic.py --out "$OUT"; fi
+if [ -z "${1:-}" ] || [[ "$ARG" == *,spp,* ]]; then python tests/golden/gen_spp.py --out "$OUT"; fi
 if [ -n "$NAMES" ]; then python tests/golden/gen_golden.py --only "$NAMES" --out "$OUT"
 elif [ -z "${1:-}" ]; then python tests/golden/gen_golden.py --out "$OUT"; fi
 python - "$OUT" <<'PY'
